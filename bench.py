@@ -2,6 +2,14 @@
 """Benchmark: device-resident batched CRC-32 on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg4k|sha1|e2e|perf|verify]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`,
+`ms_per_step`, `roofline.achieved`); --dump-outputs DIR also writes the last
+timed step's raw CRCs as DIR/crc32_raw.npy.  What the rest of this text
+describes beyond that (`isolated_launch_ms`, `roofline.read_stream`, `check`,
+`cpu_baseline`, the other configs, chunk sizes and the all-devices host leg)
+runs only with --full.
 
 One "step" = one pass of the hot path over one batch: crc_update(init, chunk)
 for every chunk of the batch (main kernel + per-chunk fold), inputs already
@@ -63,7 +71,34 @@ def parse():
                    help="cfg2 only: skip the 4 KiB (cfg4k) and 4 MiB (cfg4) lines reported in 'other_chunk_sizes'")
     p.add_argument("--ramp-ms", type=float, default=200.0,
                    help="untimed device ramp before the warmup steps (clocks/TLB; not counted as steps)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure: checks against the golden digests and zlib, "
+                        "CPU baselines, isolated launches, the read-only ceiling, the two-stream ring, the "
+                        "other configs and chunk sizes, the all-devices host leg (--no-cpu / --no-extra "
+                        "take their parts out again)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                        "(float64; inputs are seeded, so two builds can be compared output for output)")
+    args = p.parse_args()
+    if args.dump_outputs and args.config in ("perf", "multi"):
+        p.error(f"--dump-outputs: --config {args.config} returns no arrays")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_extra = True
+    return args
+
+
+def dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: the arrays a caller of the timed path received in
+    the last timed step, one DIR/<name>.npy each (float64: every u8 / u32 /
+    i32 value is exact in it), `_rank<r>` appended at N > 1."""
+    if not getattr(args, "dump_outputs", None):
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        if world > 1:
+            name = f"{name}_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a).astype(np.float64))
 
 
 def pg_timeout_s():
@@ -498,9 +533,94 @@ def run_crc(args, rank, world, device, dist):
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed, dist, device)
     kernel_ms = lib.cio_gpu_event_elapsed_ms(ev0, ev1) / args.steps
-    outs_ref = [o.cpu().numpy().copy() for o in outs]
     lib.cio_gpu_event_destroy(ev0)
     lib.cio_gpu_event_destroy(ev1)
+    # the last timed step's result as its caller receives it: one raw CRC per chunk
+    dump_outputs(args, rank, world, {"crc32_raw": outs[(args.steps - 1) % nrot].cpu().numpy().view(np.uint32)})
+    full = getattr(args, "full", False)
+    wgs = plan.workgroups     # the plan's grid (one or four workgroups per CU)
+    if full:
+        nd, launch_ms, nrs, rs_ms, rs_gbs, pipelined = crc_diagnostics(args, plan, bufs, outs, offs, lens, total,
+                                                                       stream, device)
+
+    bytes_rank = int(lens.sum())
+    # weak: every rank holds an equal shard; strong (cfg4): the whole 8192-chunk job
+    bytes_all = bytes_rank * world if scaling == "weak" else int(wl.CFG4_N * wl.CFG4_LEN)
+    value = bytes_all * args.steps / elapsed / 1e9
+    achieved = bytes_rank / (kernel_ms * 1e-3) / 1e9
+
+    res = {
+        "metric": METRIC if args.config == "cfg2" else f"device-resident CRC32 GB/s ({args.config})",
+        "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "device_ramp": {"ms": args.ramp_ms, "launches": ramp_n,
+                        "note": "untimed launches before the warmup steps so short --warmup values do not "
+                                "time a cold device"},
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic (splitmix64 uniform random bytes, generated in HBM)",
+        "config": {**desc, "parallelism": f"replicas/shards x{world}, no collective on the data path",
+                   "rotating_batches": nrot},
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "traffic": load_pmc_traffic(args.config, bytes_rank),
+                     "traffic_source": (f"profiles/pmc_{args.config}.json: HBM bytes per launch of this kernel "
+                                        "from a committed rocprofv3 --pmc pass (FETCH_SIZE x2 gfx950 "
+                                        "correction + WRITE_SIZE, separate passes; its traffic/algorithmic "
+                                        "ratio when this launch's size differs); not measured in this run")
+                     if load_pmc_traffic(args.config, bytes_rank) is not None else None,
+                     "kernel": plan.kernel_name(), "kernel_ms_mean": round(kernel_ms, 5),
+                     "timing": "HIP event pair on the launch stream around the K back-to-back timed "
+                               "launches, divided by K (launch gaps included)",
+                     "algorithmic_bytes_per_launch": bytes_rank,
+                     "workgroups": wgs},
+    }
+    if full:
+        res["roofline"].update({
+            "isolated_launch_ms": {"mean": round(float(launch_ms.mean()), 5),
+                                   "median": round(float(np.median(launch_ms)), 5),
+                                   "min": round(float(launch_ms.min()), 5),
+                                   "note": f"{nd} launches each bracketed by its own event pair, "
+                                           "after the timed region"},
+            "read_stream": {"GBps": round(rs_gbs, 1), "ms": round(rs_ms, 5), "workgroups": wgs,
+                            "note": "read-only kernel, same grid/loads/buffers, "
+                                    f"{nrs} back-to-back launches under one event pair"},
+            "frac_of_read_stream": round(achieved / rs_gbs, 4)})
+        # Correctness of the timed pass: batch 0 (seed) vs golden / CPU reference.
+        res["check"], gpu0 = crc_checks(args, rank, world, dist, plan, bufs, outs, offs, lens, ids, seed,
+                                        stream, device)
+        if pipelined is not None:
+            res["pipelined_two_streams"] = pipelined
+    if world > 1:
+        # SURVEY §8(e): per-GPU rates beside the aggregate `value`.
+        res["per_gpu"] = {"achieved_GBps": [round(v, 1) for v in gather_over_ranks(achieved, dist, device)],
+                          "kernel_ms_mean": [round(v, 5) for v in gather_over_ranks(kernel_ms, dist, device)],
+                          "note": "rank order; each rank's algorithmic bytes / its kernel time"}
+    # The reference CPU path beside the line at every N (rank 0, its own
+    # shard: the same per-GPU batch), 1 thread plus the per-GPU CPU share.
+    if rank == 0 and not args.no_cpu and args.config == "cfg2":
+        host = bufs[0].cpu().numpy()
+        res["cpu_baseline"] = cpu_baseline(host, offs, lens, gpu0, world=world)
+    if rank == 0 and args.config in ("cfg3", "cfg4", "cfg4k") and not getattr(args, "no_cpu_sample", args.no_cpu):
+        try:
+            res["cpu_baseline"] = cpu_sample_baseline(bufs[0], offs, lens, gpu0, world=world)
+        except Exception as e:  # informational
+            res["cpu_baseline"] = {"error": str(e)}
+    if "cpu_baseline" in res and world > 1:
+        res["cpu_baseline"]["shard"] = f"rank 0's shard of the {world}-GPU job (the per-GPU batch)"
+    plan.close()
+    return res
+
+
+def crc_diagnostics(args, plan, bufs, outs, offs, lens, total, stream, device):
+    """--full: what run_crc measures beside its timed region, after it, over
+    the same plan and rotating buffers: isolated launches, the read-only
+    ceiling and (cfg2) the two-stream ring."""
+    import torch
+    import chunkio_amd as cio
+    lib = cio.lib()
+    sptr = int(stream.cuda_stream)
+    nrot = len(bufs)
+    outs_ref = [o.cpu().numpy().copy() for o in outs]
 
     # Diagnostic (after the timed region): launches each bracketed by their
     # own event pair -- the per-launch distribution, isolated launches.
@@ -560,14 +680,15 @@ def run_crc(args, rank, world, device, dist):
                      "note": "K batches through cio_crc32_ring (2 plans, own streams), joined on the launch "
                              "stream: launch tails overlap the next batch; a deployment figure, not `value` "
                              "(kernel durations overlap)"}
+    return nd, launch_ms, nrs, rs_ms, rs_gbs, pipelined
 
-    bytes_rank = int(lens.sum())
-    # weak: every rank holds an equal shard; strong (cfg4): the whole 8192-chunk job
-    bytes_all = bytes_rank * world if scaling == "weak" else int(wl.CFG4_N * wl.CFG4_LEN)
-    value = bytes_all * args.steps / elapsed / 1e9
-    achieved = bytes_rank / (kernel_ms * 1e-3) / 1e9
 
-    # Correctness of the timed pass: batch 0 (seed) vs golden / CPU reference.
+def crc_checks(args, rank, world, dist, plan, bufs, outs, offs, lens, ids, seed, stream, device):
+    """--full: batch 0 through the timed path once more, against the golden
+    digests, zlib and (N > 1) the regenerated shard.  Returns (check, the
+    batch's raw CRCs)."""
+    import torch
+    from chunkio_amd import workloads as wl
     plan.exec(bufs[0], outs[0], stream=stream)
     torch.cuda.synchronize(device)
     gpu0 = outs[0].cpu().numpy().view(np.uint32).copy()
@@ -629,63 +750,7 @@ def run_crc(args, rank, world, device, dist):
         want = [zlib.crc32(wl.gen_chunk(seed, int(ids[i]), int(lens[i]))) ^ 0xFFFFFFFF for i in range(k)]
         ok = [int(x) for x in gpu0[:k]] == want
         check["shard_sample_zlib_match_all_ranks"] = max_over_ranks(0.0 if ok else 1.0, dist, device) == 0.0
-
-    res = {
-        "metric": METRIC if args.config == "cfg2" else f"device-resident CRC32 GB/s ({args.config})",
-        "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "device_ramp": {"ms": args.ramp_ms, "launches": ramp_n,
-                        "note": "untimed launches before the warmup steps so short --warmup values do not "
-                                "time a cold device"},
-        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic (splitmix64 uniform random bytes, generated in HBM)",
-        "config": {**desc, "parallelism": f"replicas/shards x{world}, no collective on the data path",
-                   "rotating_batches": nrot},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": load_pmc_traffic(args.config, bytes_rank),
-                     "traffic_source": (f"profiles/pmc_{args.config}.json: HBM bytes per launch of this kernel "
-                                        "from a committed rocprofv3 --pmc pass (FETCH_SIZE x2 gfx950 "
-                                        "correction + WRITE_SIZE, separate passes; its traffic/algorithmic "
-                                        "ratio when this launch's size differs); not measured in this run")
-                     if load_pmc_traffic(args.config, bytes_rank) is not None else None,
-                     "kernel": plan.kernel_name(), "kernel_ms_mean": round(kernel_ms, 5),
-                     "timing": "HIP event pair on the launch stream around the K back-to-back timed "
-                               "launches, divided by K (launch gaps included)",
-                     "isolated_launch_ms": {"mean": round(float(launch_ms.mean()), 5),
-                                            "median": round(float(np.median(launch_ms)), 5),
-                                            "min": round(float(launch_ms.min()), 5),
-                                            "note": f"{nd} launches each bracketed by its own event pair, "
-                                                    "after the timed region"},
-                     "algorithmic_bytes_per_launch": bytes_rank,
-                     "workgroups": wgs,
-                     "read_stream": {"GBps": round(rs_gbs, 1), "ms": round(rs_ms, 5), "workgroups": wgs,
-                                     "note": "read-only kernel, same grid/loads/buffers, "
-                                             f"{nrs} back-to-back launches under one event pair"},
-                     "frac_of_read_stream": round(achieved / rs_gbs, 4)},
-        "check": check,
-    }
-    if pipelined is not None:
-        res["pipelined_two_streams"] = pipelined
-    if world > 1:
-        # SURVEY §8(e): per-GPU rates beside the aggregate `value`.
-        res["per_gpu"] = {"achieved_GBps": [round(v, 1) for v in gather_over_ranks(achieved, dist, device)],
-                          "kernel_ms_mean": [round(v, 5) for v in gather_over_ranks(kernel_ms, dist, device)],
-                          "note": "rank order; each rank's algorithmic bytes / its kernel time"}
-    # The reference CPU path beside the line at every N (rank 0, its own
-    # shard: the same per-GPU batch), 1 thread plus the per-GPU CPU share.
-    if rank == 0 and not args.no_cpu and args.config == "cfg2":
-        host = bufs[0].cpu().numpy()
-        res["cpu_baseline"] = cpu_baseline(host, offs, lens, gpu0, world=world)
-    if rank == 0 and args.config in ("cfg3", "cfg4", "cfg4k") and not getattr(args, "no_cpu_sample", args.no_cpu):
-        try:
-            res["cpu_baseline"] = cpu_sample_baseline(bufs[0], offs, lens, gpu0, world=world)
-        except Exception as e:  # informational
-            res["cpu_baseline"] = {"error": str(e)}
-    if "cpu_baseline" in res and world > 1:
-        res["cpu_baseline"]["shard"] = f"rank 0's shard of the {world}-GPU job (the per-GPU batch)"
-    plan.close()
-    return res
+    return check, gpu0
 
 
 def run_sha1(args, rank, world, device, dist):
@@ -714,6 +779,7 @@ def run_sha1(args, rank, world, device, dist):
     elapsed = max_over_ranks(time.perf_counter() - t0, dist, device)
     value = int(lens.sum()) * world * args.steps / elapsed / 1e9
     got = digests.cpu().numpy().reshape(-1, 20)
+    dump_outputs(args, rank, world, {"sha1_digests": got})
     sample = sorted({0, len(lens) // 2, len(lens) - 1})
     check = {"hashlib_match": all(
         bytes(got[i]) == hashlib.sha1(wl.gen_chunk(seed, int(ids[i]) if ids is not None else i,
@@ -898,6 +964,7 @@ def run_e2e(args, rank, world, device, dist):
     barrier(dist)
     elapsed = max_over_ranks(time.perf_counter() - t0, dist, device)
     value = int(lens.sum()) * world * steps / elapsed / 1e9
+    dump_outputs(args, rank, world, {"crc32_raw": np.asarray(out, dtype=np.uint32)})
     legs_staged = cio.pipe_last_timing()
     # Same batch with the host buffer pinned in place once (long-lived chunk
     # mappings): the pipeline DMAs it directly, no staging copy.
@@ -1234,6 +1301,7 @@ def run_verify(args, rank, world, device, dist, compact=False):
             st, er, cr = cf.verify_paths(paths)
             times.append(time.perf_counter() - t0)
         t = min(times)
+        dump_outputs(args, rank, world, {"verify_status": st, "verify_errno": er, "verify_crc32_raw": cr})
         ok_idx = [i for i in range(files) if i != bad]
         check = {"good_files_ok": bool(np.all(st[ok_idx] == 0)),
                  "good_crc_088740e7": bool(np.all((cr[ok_idx] ^ 0xFFFFFFFF) == 0x088740E7)),
@@ -1545,6 +1613,7 @@ def other_chunk_sizes(args, rank, world, device, dist):
         a = copy.copy(args)
         a.config, a.steps, a.warmup, a.no_cpu = cfg, steps, warm, True
         a.no_cpu_sample = args.no_cpu
+        a.dump_outputs = None        # the headline's outputs only
         r = run_crc(a, rank, world, device, dist)
         out[cfg] = {"value": r["value"], "unit": r["unit"], "scaling": r["scaling"], "steps": steps,
                     "warmup": warm, "ms_per_step": r["ms_per_step"], "workload": r["config"]["workload"],
@@ -1700,6 +1769,7 @@ def other_configs(args, rank, world, device, dist, only=None):
         a.config, a.steps, a.warmup = cfg, steps, warm
         a.no_cpu = cfg not in ("verify", "sha1") or args.no_cpu
         a.no_cpu_sample = args.no_cpu
+        a.dump_outputs = None        # the headline's outputs only
         t1 = time.perf_counter()
         if cfg == "sha1":
             r = run_sha1(a, rank, world, device, dist)

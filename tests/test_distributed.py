@@ -476,3 +476,71 @@ def test_bench_multi_device_leg_rank0_alone_gloo_world2():
     assert bench.multi_device_list(4, 2, True) == ([0, 1, 0, 1], True)
     assert bench.multi_device_list(2, 1, False) == (None, True)
     assert bench.multi_device_list(1, 1, False) == ([0], False)
+
+
+def test_bench_plain_and_full_options(monkeypatch, tmp_path):
+    """A plain command line runs none of the legs beside the headline
+    (no_cpu / no_extra forced on); --full leaves them to --no-cpu / --no-extra.
+    --dump-outputs writes each array as float64, per rank at N > 1, and
+    nothing when the option is absent."""
+    import argparse
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert a.no_cpu and a.no_extra
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu and not a.no_extra
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu"])
+    a = bench.parse()
+    assert a.full and a.no_cpu and not a.no_extra
+
+    crc = np.array([0, 1, 0xFFFFFFFF, 0x088740E7], dtype=np.uint32)
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), 0, 1, {"crc32_raw": crc})
+    assert list(tmp_path.iterdir()) == []
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(argparse.Namespace(dump_outputs=str(d)), 0, 1, {"crc32_raw": crc})
+    got = np.load(d / "crc32_raw.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), crc)
+    bench.dump_outputs(argparse.Namespace(dump_outputs=str(d)), 1, 2, {"crc32_raw": crc.astype(np.int32)})
+    got = np.load(d / "crc32_raw_rank1.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), crc.astype(np.int32))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(cuda, golden, tmp_path):
+    """`bench.py --gpus 1 --steps 1 --warmup 0 --dump-outputs DIR`: one JSON
+    line with the headline fields and none of the --full legs, and the one
+    timed step's raw CRCs (batch 0 of the seeded cfg2 job) as float64 in
+    DIR/crc32_raw.npy, equal to the golden digest of that batch."""
+    import hashlib
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1",
+                        "--warmup", "0", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 1 and line["warmup"] == 0 and line["n_gpus"] == 1
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["ms_per_step"] > 0
+    # value = the batch's bytes over the one step's wall time; ms_per_step is rounded to 1e-4 ms
+    # and cannot be under bytes / 8 TB/s = 0.052 ms, so the two agree within 5e-5 / 0.052 < 2e-3
+    assert line["value"] == pytest.approx(wl.CFG2_N * wl.CFG2_LEN / (line["ms_per_step"] * 1e-3) / 1e9, rel=2e-3)
+    for leg in ("check", "cpu_baseline", "pipelined_two_streams", "other_configs", "other_chunk_sizes",
+                "multi_device_host", "diagnostic_batches"):
+        assert leg not in line, leg
+    assert "read_stream" not in line["roofline"] and "isolated_launch_ms" not in line["roofline"]
+    assert sorted(os.listdir(out_dir)) == ["crc32_raw.npy"]
+    got = np.load(out_dir / "crc32_raw.npy")
+    assert got.dtype == np.float64 and got.shape == (wl.CFG2_N,)
+    assert hashlib.sha256(got.astype("<u4").tobytes()).hexdigest() == golden["cfg2"]["sha256_of_raw_le"]

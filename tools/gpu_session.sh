@@ -10,7 +10,8 @@
 #   smoke                   __graft_entry__.smoke()
 #   bench[:ARGS]            python bench.py ARGS ('+' for spaces) -> bench_<n>.json
 #   prof:CFG:STEPS:WARMUP[:ARGS]
-#                           rocprofv3 --kernel-trace --stats of bench.py --config CFG
+#                           rocprofv3 --kernel-trace --stats of bench.py --config CFG --full
+#                           (the launch sequence tools/prof_pair.py and prof_window.py expect)
 #   pmc:CFG:COUNTERS        one rocprofv3 --pmc pass (COUNTERS comma-separated)
 #   traffic:CFG             FETCH_SIZE and WRITE_SIZE passes + tools/pmc_traffic.py
 #   py:SCRIPT[:ARGS]        python SCRIPT ARGS (a probe or measurement tool)
@@ -48,7 +49,7 @@ for step in "$@"; do
     prof)
       IFS=: read -r cfg steps warm args <<< "$rest"
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_${cfg}_$n" -o run --output-format csv -- \
-          python3 bench.py --config "$cfg" --steps "${steps:-300}" --warmup "${warm:-200}" --no-cpu --no-extra ${args//+/ } \
+          python3 bench.py --config "$cfg" --steps "${steps:-300}" --warmup "${warm:-200}" --full --no-cpu --no-extra ${args//+/ } \
           > "$O/bench_prof_${cfg}_$n.json" 2> "$O/prof_${cfg}_$n.err"
       stop_if_failed $? "prof $cfg" ;;
     pmc)

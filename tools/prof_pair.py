@@ -8,7 +8,8 @@ that roofline.frac can be recomputed from the committed profile (VERDICT r2
 The timed window is located from the end of the kernel's dispatch list:
 bench.py launches the kernel during an untimed device ramp, then `warmup`
 times, then `steps` timed launches back to back, then `iso` isolated
-diagnostic launches (min(steps, 100) for the CRC lines, 0 for SHA-1).
+diagnostic launches (min(steps, 100) for the CRC lines of `bench.py --full`,
+0 for SHA-1 and for a run without --full).
 Prints JSON: the timed window's mean / median kernel duration from rocprof,
 the bench line's own event mean, algorithmic bytes / rocprof mean as GB/s and
 as a fraction of 8 TB/s, its ratio to the line's roofline.frac, and whether
@@ -28,7 +29,8 @@ def main():
     with open(bench_path) as f:
         line = json.loads([x for x in f.read().splitlines() if x.startswith("{")][-1])
     steps, warm = int(line["steps"]), int(line["warmup"])
-    iso = int(sys.argv[4]) if len(sys.argv) > 4 else min(steps, 100)
+    ran_iso = "isolated_launch_ms" in line.get("roofline", {})
+    iso = int(sys.argv[4]) if len(sys.argv) > 4 else (min(steps, 100) if ran_iso else 0)
     rows = [r for r in csv.DictReader(open(trace)) if name in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     d = np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows])

@@ -3,9 +3,10 @@
 
     python tools/prof_window.py <run_kernel_trace.csv> <warmup> <steps> [kernel-substring]
 
-bench.py launches the CRC kernel during an untimed device ramp, then `warmup`
-times, then `steps` timed launches back to back, then min(steps, 100)
-isolated diagnostic launches (phases are located from the end).  Prints the
+bench.py --full launches the CRC kernel during an untimed device ramp, then
+`warmup` times, then `steps` timed launches back to back, then min(steps, 100)
+isolated diagnostic launches (phases are located from the end; a trace of a
+run without --full has no isolated launches and does not fit).  Prints the
 mean / median / min duration of each phase (dispatches in start order) so the
 timed window can be compared with bench.py's `kernel_ms_mean`.
 """
