@@ -13,11 +13,13 @@ Layers:
 """
 from ._lib import LIB_PATH, CioGpuError, lib  # noqa: F401
 from .crc32 import (  # noqa: F401
-    CRC_INIT, Crc32Plan, Crc32Ring, crc32, crc32_batch_cpu_packed, crc32_batch_dev, crc32_batch_host, crc32_batch_host_packed,
+    CRC_INIT, DEVPLAN_E_BATCH_TOO_LARGE, DEVPLAN_E_BOUNDS, DEVPLAN_E_CHUNK_TOO_LARGE, Crc32DevPlan, Crc32Plan, Crc32Ring, crc32, crc32_batch_cpu_packed, crc32_batch_dev, crc32_batch_host, crc32_batch_host_packed,
     crc32_combine, crc32_split_host, host_threads,
     crc32_shift, crc_finalize, crc_init, crc_update, device_count, fill_synthetic, host_register,
     host_unregister, pipe_last_timing, plan_cache_stats, split_rates, route, Sha1, sha1_hash, sha1_to_hex, sha1_batch_dev, sha1_batch_dev_async, sha1_final_batch_dev,
     sha1_states_init, sha1_states_view, sha1_update_batch_dev,
 )
+
+from .chunkfile import verify_batch_dev  # noqa: F401,E402
 
 __version__ = "0.5.0"

@@ -22,6 +22,7 @@ EXPORTS = (
     "cio_crc32_plan_create", "cio_crc32_plan_destroy", "cio_crc32_plan_exec",
     "cio_crc32_plan_exec_events", "cio_crc32_plan_bytes", "cio_crc32_plan_kernel", "cio_crc32_plan_workgroups", "cio_crc32_ring_create", "cio_crc32_ring_exec",
     "cio_crc32_ring_join", "cio_crc32_ring_destroy", "cio_crc32_batch_dev", "cio_crc32_batch_host",
+    "cio_crc32_devplan_create", "cio_crc32_devplan_destroy", "cio_crc32_devplan_exec", "cio_crc32_devplan_workgroups",
     "cio_crc32_batch_host_multi", "cio_crc32_split_host_multi", "cio_crc32_batch_fd_multi", "cio_gpu_device_count", "cio_gpu_set_device", "cio_gpu_get_device", "cio_gpu_numa_node",
     "cio_gpu_pci_bus_id", "cio_gpu_plan_cache_stats",
     "cio_crc32_host_register", "cio_crc32_host_unregister", "cio_gpu_pipe_last_timing",
@@ -37,6 +38,7 @@ EXPORTS = (
     "cioa_SHA1_Init", "cioa_SHA1_Update", "cioa_SHA1_Final",
     # include/chunkio_amd/cio_verify.h
     "cio_file_verify_batch", "cio_file_verify_batch_multi", "cio_verify_paths", "cio_verify_paths_multi",
+    "cio_file_verify_batch_dev",
     # include/chunkio_amd/cio_sync.h
     "cio_file_sync_batch", "cio_file_sync_batch_multi", "cio_file_sync_batch_begin", "cio_file_sync_batch_end",
     # include/chunkio_amd/cioa_chunk.h
@@ -85,6 +87,12 @@ def _bind(lib):
         "cio_crc32_ring_join": (ctypes.c_int, [V, V]),
         "cio_crc32_ring_destroy": (None, [V]),
         "cio_crc32_batch_dev": (ctypes.c_int, [V, c_u64_p, c_u64_p, V, V, ctypes.c_size_t, V]),
+        "cio_crc32_devplan_create": (ctypes.c_int, [P(V), ctypes.c_size_t]),
+        "cio_crc32_devplan_destroy": (None, [V]),
+        "cio_crc32_devplan_exec": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V, V, V]),
+        "cio_crc32_devplan_workgroups": (ctypes.c_uint32, [V]),
+        "cio_file_verify_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int,
+                                                     V, V, V, V, V, V]),
         "cio_crc32_batch_host": (ctypes.c_int, [P(V), P(ctypes.c_size_t), c_u32_p, c_u32_p,
                                                 ctypes.c_size_t]),
         "cio_crc32_batch_host_multi": (ctypes.c_int, [P(V), P(ctypes.c_size_t), c_u32_p, c_u32_p,

@@ -154,6 +154,30 @@ def verify_paths(paths, flags=CIO_CHECKSUM, devices=None):
     return st[:n], er[:n], cr[:n]
 
 
+def verify_batch_dev(plan, base, img_offs, img_sizes, flags=CIO_CHECKSUM, stream=None):
+    """Verify-on-load of chunk images that are in device memory
+    (cio_file_verify_batch_dev): image i is base[img_offs[i]:img_offs[i] +
+    img_sizes[i]].  plan: a crc32.Crc32DevPlan with max_chunks >= n; base: uint8
+    cuda tensor; img_offs, img_sizes: 64-bit cuda tensors.  Queues the work on
+    `stream` and returns cuda tensors (status int32, error int32, crc_raw
+    int32 holding the uint32 bits, meta_len int32, content_len int64) without
+    waiting for them."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    dev = base.device
+    st = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    er = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    cr = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    ml = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    cl = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    rc = _lib.lib().cio_file_verify_batch_dev(plan._handle, _ptr(base), base.numel() * base.element_size(),
+                                              _ptr(img_offs), _ptr(img_sizes), n, int(flags), _ptr(st), _ptr(er),
+                                              _ptr(cr), _ptr(ml), _ptr(cl), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_verify_batch_dev")
+    return st[:n], er[:n], cr[:n], ml[:n], cl[:n]
+
+
 class Context:
     """cio_ctx: a root directory of streams of chunk files."""
 

@@ -181,6 +181,61 @@ class Crc32Ring:
         self.close()
 
 
+DEVPLAN_E_BOUNDS, DEVPLAN_E_CHUNK_TOO_LARGE, DEVPLAN_E_BATCH_TOO_LARGE = 1, 2, 4
+
+
+class Crc32DevPlan:
+    """A device-planned batch (cio_crc32_devplan_*): arenas for up to
+    max_chunks chunks; the geometry comes from int64/uint64 cuda tensors at
+    run time, so exec() allocates nothing, does not synchronise, and can be
+    captured in a graph whose replays follow the tensors' contents.  Not
+    thread-safe; one exec in flight at a time."""
+
+    def __init__(self, max_chunks):
+        self.max_chunks = int(max_chunks)
+        handle = ctypes.c_void_p()
+        _lib.check(_lib.lib().cio_crc32_devplan_create(ctypes.byref(handle), self.max_chunks),
+                   "cio_crc32_devplan_create")
+        self._handle = handle
+        import torch
+        self._status = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+
+    @property
+    def workgroups(self):
+        return int(_lib.lib().cio_crc32_devplan_workgroups(self._handle))
+
+    def exec(self, base, offs, lens, out, seeds=None, n=None, stream=None):
+        """base: uint8 cuda tensor (its size is the device-side bound); offs,
+        lens: 64-bit cuda tensors; out: int32/uint32 cuda tensor of n; seeds:
+        same or None.  n defaults to len(offs)."""
+        n = int(offs.numel()) if n is None else int(n)
+        _lib.check(_lib.lib().cio_crc32_devplan_exec(self._handle, _ptr(base), base.numel() * base.element_size(),
+                                                     _ptr(offs), _ptr(lens), n, _ptr(seeds), _ptr(out),
+                                                     _ptr(self._status), _stream_ptr(stream)),
+                   "cio_crc32_devplan_exec")
+
+    def status(self):
+        """The last exec's device status word (0 or DEVPLAN_E_* bits); waits for it."""
+        return int(self._status.cpu().numpy().view(np.uint32)[0])
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.lib().cio_crc32_devplan_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def _to_u32_numpy(t):
     return t.cpu().numpy().view(np.uint32).copy()
 

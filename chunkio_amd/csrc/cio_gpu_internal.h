@@ -93,9 +93,32 @@ int plan_exec_impl(const cio_crc32_plan *p, const void *dev_base, const uint32_t
                    uint32_t *dev_out, const uint32_t *cid, hipStream_t s,
                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
+
+// ---- device-planned batches (devplan_gpu.hip) ----
+// The planner's device header, 64-bit words: the stream kernel's DEVHDR
+// instantiation reads S and ntiny from it.
+constexpr int kDevHdrS = 0, kDevHdrNtiny = 1, kDevHdrBytes = 2, kDevHdrStatus = 3, kDevHdrWords = 4;
+constexpr uint32_t kPlanBlock = 1024;       // chunks per planner workgroup (one per thread)
+
+// Per planner workgroup: its chunks' totals, then (after the scan) the totals
+// of every workgroup before it.
+struct PlanBlockSum {
+    uint64_t steps, bytes;
+    uint32_t ntiny, err;
+};
+
+// The planner kernels (serial chain on s): everything plan_build writes, from
+// device offs/lens, into dp's arenas.  n >= 1.
+int devplan_launch_planner(const cio_crc32_devplan *dp, uint64_t dev_bytes, const uint64_t *dev_offs,
+                           const uint64_t *dev_lens, size_t n, uint32_t *dev_status, hipStream_t s);
+// One launch of the general stream kernel over the plan image in p's arrays,
+// S and ntiny from the device header hdr (crc32_gpu.hip).
+int devplan_crc_launch(const cio_crc32_plan *p, const unsigned long long *hdr, const void *dev_base,
+                       const uint32_t *dev_seeds, uint32_t *dev_out, size_t n, hipStream_t s);
+
 }  // namespace cioa
 
-#define HIP_TRY(expr, what)                                \
+#define HIP_TRY(expr, what)                             \
     do {                                                   \
         hipError_t e_ = (expr);                            \
         if (e_ != hipSuccess) return cioa::fail(what, e_); \
@@ -123,6 +146,18 @@ struct cio_crc32_plan {
     uint32_t *counters = nullptr;
     uint32_t *pfac = nullptr;   // per piece slot: x^(8 * chunk bytes after the piece)
     cioa::DeviceState *st = nullptr;
+};
+
+// A device-planned batch: plan_init's grid and knobs, arenas for max_chunks
+// chunks (the plan image lives in `p`'s arrays), the planner's scratch and
+// header, and the verify-on-load arrays (CRC regions and raw CRCs).
+struct cio_crc32_devplan {
+    cio_crc32_plan *p = nullptr;
+    uint32_t max_chunks = 0;
+    cioa::PlanBlockSum *bsum = nullptr;      // ceil(max_chunks / kPlanBlock)
+    unsigned long long *hdr = nullptr;       // kDevHdrWords
+    uint64_t *roffs = nullptr, *rlens = nullptr;   // cio_file_verify_batch_dev: CRC regions
+    uint32_t *rcrc = nullptr;
 };
 
 #endif

@@ -674,9 +674,17 @@ __device__ __forceinline__ void rotate_prio(uint32_t slot_group, uint64_t it)
 // the next step's loads are issued as soon as this step's data has landed,
 // BEFORE its CRC -- still one step (4 KiB) in flight per wave, as in the
 // read-only stream, but no longer none while the wave computes.
-template <bool STAMPS = false, int PRIO = 1, bool UNIFORM = false, bool AHEAD = false, bool L64 = false>
+// DEVHDR (device-planned batches, devplan_gpu.hip): the plan was written by
+// planner kernels earlier on the stream, so the host knows neither S nor
+// ntiny.  This instantiation ignores both arguments and reads them from the
+// planner's header (kDevHdr* words), whose address arrives in the last
+// argument (`stamps`, which only STAMPS instantiations use otherwise): the
+// parameter list, and with it the preloaded first nine arguments, is the same
+// for every instantiation.  General path only (not UNIFORM, not AHEAD).
+template <bool STAMPS = false, int PRIO = 1, bool UNIFORM = false, bool AHEAD = false, bool L64 = false,
+          bool DEVHDR = false>
 __global__ void __launch_bounds__(kThreads, 1)
-crc32_stream_kernel(const uint8_t *base, uint64_t S, uint64_t ustride, uint64_t ua0, uint64_t uvlen,
+crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint64_t ua0, uint64_t uvlen,
                     uint32_t W, uint32_t unsteps, uint32_t uh, uint32_t n,
                     const ChunkDesc *__restrict__ desc,
                     const WaveStart *__restrict__ wstart, const uint32_t *__restrict__ tiny,
@@ -684,10 +692,13 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S, uint64_t ustride, uint64_t 
                     unsigned long long *__restrict__ partials, uint32_t *__restrict__ counters,
                     const uint32_t *__restrict__ g_slice, const uint32_t *__restrict__ g_shift,
                     const uint32_t *__restrict__ g_x8, const uint32_t *__restrict__ pfac,
-                    uint32_t ntiny, unsigned long long *stamps)
+                    uint32_t ntiny_arg, unsigned long long *stamps)
 {
+    static_assert(!DEVHDR || (!STAMPS && !UNIFORM && !AHEAD), "device-planned batches take the general path");
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     const uint32_t tid = threadIdx.x;
+    const uint64_t S = DEVHDR ? uniform_u64(stamps[kDevHdrS]) : S_arg;
+    const uint32_t ntiny = DEVHDR ? __builtin_amdgcn_readfirstlane((uint32_t) stamps[kDevHdrNtiny]) : ntiny_arg;
     unsigned long long t_entry = 0, t_tables = 0, t_stream = 0, t_first = 0, t_mid = 0, t_issued = 0;
     unsigned long long t_wt[2] = {0, 0}, t_step1 = 0, t_arrived = 0, t_bar1 = 0, t_bar2 = 0, t_folded = 0;
     if (STAMPS) {
@@ -2540,6 +2551,29 @@ int cioa::plan_exec_impl(const cio_crc32_plan *p, const void *dev_base, const ui
     if (ev1) {
         HIP_TRY(hipEventRecord(ev1, s), "hipEventRecord");
     }
+    return CIO_OK;
+}
+
+// The launch of a device-planned batch: the general stream kernel (DEVHDR
+// instantiation) on plan_init's grid, one workgroup per CU (CIO_GPU_GRID under
+// CIO_GPU_DIAG=1 honoured), with plan_init's L64 and priority settings.  The
+// small-chunk kernel, the 4x-oversubscribed grid and the anti-camping grid are
+// host decisions that need S, which only the device knows here: this path
+// takes none of them.
+int cioa::devplan_crc_launch(const cio_crc32_plan *p, const unsigned long long *hdr, const void *dev_base,
+                             const uint32_t *dev_seeds, uint32_t *dev_out, size_t n, hipStream_t s)
+{
+    const DeviceState *st = p->st;
+    StreamKernel kern = p->l64 ? (p->prio ? crc32_stream_kernel<false, 1, false, false, true, true>
+                                          : crc32_stream_kernel<false, 0, false, false, true, true>)
+                               : (p->prio ? crc32_stream_kernel<false, 1, false, false, false, true>
+                                          : crc32_stream_kernel<false, 0, false, false, false, true>);
+    hipLaunchKernelGGL(kern, dim3(p->grid), dim3(kThreads), 0, s,
+                       reinterpret_cast<const uint8_t *>(dev_base), (uint64_t) 0, (uint64_t) 0, (uint64_t) 0,
+                       (uint64_t) 0, p->W, 0u, 0u, (uint32_t) n, p->desc, p->wstart, p->tiny,
+                       dev_seeds, dev_out, (const uint32_t *) nullptr, p->partials, p->counters, st->slice,
+                       st->shift, st->x8, p->pfac, 0u, const_cast<unsigned long long *>(hdr));
+    HIP_TRY(hipGetLastError(), "crc32_stream_kernel (device-planned) launch");
     return CIO_OK;
 }
 

@@ -21,6 +21,11 @@
  *                                    cio_chunk_open -> cio_file_format_check
  *                                    (src/cio_scan.c:105, src/cio_file.c:266-290)
  *                                    for device-resident chunk contents
+ *   cio_crc32_devplan_create/exec()  the same loop where each chunk's offset and
+ *                                    length are themselves in device memory
+ *                                    (e.g. the content length field of a chunk
+ *                                    header, include/chunkio/cio_file_st.h:
+ *                                    129-179, of an image that is in HBM)
  *   cio_crc32_batch_host()           the same over host (e.g. mmap'd) buffers:
  *                                    pinned staging + H2D + kernel + D2H
  *   cio_crc32_shift/_combine()       no reference counterpart; folds GPU partial
@@ -155,6 +160,58 @@ uint32_t cio_crc32_plan_workgroups(const cio_crc32_plan *plan);
 int  cio_crc32_batch_dev(const void *dev_base, const uint64_t *offs,
                          const uint64_t *lens, const uint32_t *dev_seeds,
                          uint32_t *dev_out, size_t n, void *stream);
+
+/* ---- batched CRC-32, geometry in device memory ---------------------------
+ *
+ * A device-planned batch: offs/lens are DEVICE arrays, read at run time.
+ * Planner kernels write, into arenas allocated once, the very work partition
+ * cio_crc32_plan_create builds on the host; ONE launch of the general stream
+ * kernel follows.  Use it where the host does not know the geometry (a CRC
+ * region length read from a chunk header that is in HBM) or where a captured
+ * graph must follow changing lengths; a host plan stays the faster choice for
+ * a geometry the host knows and reuses ("Device-planned batches").
+ *
+ * What this path gives up against a host plan: the kernel selections that
+ * need the step total S on the host.  It always runs the general stream
+ * kernel on one workgroup per CU -- not the small-chunk kernel, not the
+ * uniform / issue-ahead instantiations, not the 4x-oversubscribed grid and
+ * not the anti-camping grid.
+ *
+ * The geometry is validated on the device.  When a chunk has off + len
+ * overflowing or > dev_bytes, a chunk has more than 2^32 - 1 wave-steps, or
+ * the batch is too large (the host's "chunk too large" / "batch too large"
+ * errors), the status word is the OR of the CIO_DEVPLAN_E_* codes below and
+ * the CRC launch reads no data and writes no output.
+ *
+ * A plan is NOT thread-safe, and ONE exec at a time may be in flight on it
+ * (execs queued on one stream follow each other and are fine).  It belongs
+ * to the device that was current at create.
+ */
+typedef struct cio_crc32_devplan cio_crc32_devplan;
+
+#define CIO_DEVPLAN_E_BOUNDS           1   /* off + len overflows or > dev_bytes */
+#define CIO_DEVPLAN_E_CHUNK_TOO_LARGE  2   /* a chunk of more than 2^32 - 1 wave-steps */
+#define CIO_DEVPLAN_E_BATCH_TOO_LARGE  4   /* S >= 2^40 or S * waves >= 2^52 */
+
+/* Arenas for up to max_chunks (1 .. 2^32 - 2) chunks on the current device;
+ * the only call that allocates. */
+int  cio_crc32_devplan_create(cio_crc32_devplan **plan, size_t max_chunks);
+void cio_crc32_devplan_destroy(cio_crc32_devplan *plan);
+
+/* Planner kernels + ONE CRC launch on `stream`: no allocation, no host
+ * synchronisation, capturable; the geometry is read from device memory at
+ * run time, so a replay follows whatever dev_offs/dev_lens then hold.
+ * dev_bytes: size of the readable buffer at dev_base (bounds check on device).
+ * dev_seeds: device array of n raw seeds, or NULL for crc_init() each.
+ * dev_status: optional device word, 0 or CIO_DEVPLAN_E_* codes.
+ * n == 0 is a no-op; n > max_chunks is an error. */
+int  cio_crc32_devplan_exec(cio_crc32_devplan *plan, const void *dev_base, uint64_t dev_bytes,
+                            const uint64_t *dev_offs, const uint64_t *dev_lens, size_t n,
+                            const uint32_t *dev_seeds, uint32_t *dev_out,
+                            uint32_t *dev_status, void *stream);
+
+/* Workgroups the plan's CRC launch runs (one per CU). */
+uint32_t cio_crc32_devplan_workgroups(const cio_crc32_devplan *plan);
 
 /* ---- batched CRC-32 over host memory (end-to-end path) ----------------- */
 

@@ -108,6 +108,33 @@ int cio_verify_paths_multi(const char *const *paths, size_t n, int flags,
                            const int *devices, int ndev, int *status,
                            int *error, uint32_t *crc_raw);
 
+typedef struct cio_crc32_devplan cio_crc32_devplan;   /* cio_crc32_gpu.h */
+
+/* Verify n chunk images that are already in device memory: image i is the
+ * dev_img_sizes[i] bytes at dev_base + dev_img_offs[i] (both DEVICE arrays).
+ * The checks of cio_file_verify_batch through a read-only map with taint 0 --
+ * size 0: CIO_CORRUPTED / CIO_ERR_PERMISSION; size < 24: BAD_FILE_SIZE (before
+ * the magic check, as cio_file_st_get_content_len comes first); magic; legacy
+ * length inference (nothing is written back); 24 + meta_len + content_len <=
+ * size; the 8-byte CRC compare -- run in two per-image kernels around one
+ * cio_crc32_devplan_exec over the regions [img + 22, + 2 + meta_len +
+ * content_len), on `stream`: asynchronous, no allocation, no host
+ * synchronisation, capturable.  An image outside dev_bytes gets CIO_ERROR.
+ *
+ * plan: from cio_crc32_devplan_create(max_chunks >= n) (cio_crc32_gpu.h); its
+ *   rules hold (not thread-safe, one exec in flight).
+ * flags: 0 or CIOA_VERIFY_CHECKSUM; anything else is rejected (a device image
+ *   cannot be written back or deleted).  Without CIOA_VERIFY_CHECKSUM there is
+ *   no CRC launch and crc_raw is 0.
+ * Outputs, device arrays of n: status / error as cio_verify_item's; crc_raw set
+ * only on success; meta_len and content_len (either may be NULL) as
+ * cio_verify_item's. */
+int cio_file_verify_batch_dev(cio_crc32_devplan *plan, const void *dev_base, uint64_t dev_bytes,
+                              const uint64_t *dev_img_offs, const uint64_t *dev_img_sizes, size_t n,
+                              int flags, int32_t *dev_status, int32_t *dev_error,
+                              uint32_t *dev_crc_raw, uint32_t *dev_meta_len,
+                              uint64_t *dev_content_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

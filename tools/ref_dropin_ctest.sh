@@ -103,8 +103,10 @@ grep -h -o "$REPO/include/crc32/crc32.h" "$B"/src/CMakeFiles/chunkio-static.dir/
 # the reference's cio_sha1.h linked against both gets OpenSSL's digest
 echo "== cio_sha1 (src/cio_sha1.c compiled by the reference's CMake against include/sha1/sha1.h)"
 nm "$B"/src/libchunkio-static.a | grep -E ' [TU] (cio_sha1_hash|cioa_SHA1_Init)$' | sort -u
-nm "$B"/src/libchunkio-static.a | grep -q ' T cio_sha1_hash$' || { echo "cio_sha1.c not in chunkio"; exit 1; }
-nm "$B"/src/libchunkio-static.a | grep -q ' U cioa_SHA1_Init$' || { echo "SHA1_Init not taken from the shim"; exit 1; }
+# (grep reads nm's whole output: grep -q leaves at the first match, and under
+# pipefail nm's SIGPIPE then failed the check it had just passed)
+nm "$B"/src/libchunkio-static.a | grep ' T cio_sha1_hash$' > /dev/null || { echo "cio_sha1.c not in chunkio"; exit 1; }
+nm "$B"/src/libchunkio-static.a | grep ' U cioa_SHA1_Init$' > /dev/null || { echo "SHA1_Init not taken from the shim"; exit 1; }
 cc -O2 -std=gnu11 -DCIOA_REF_BOUNDARY -I"$REPO/include" -I"$REF/include" -o "$WORK/test_sha1_cmake" \
     "$REPO/tests/c/test_sha1.c" "$B"/src/libchunkio-static.a "$SHIM" -Wl,-rpath,"$(dirname "$SHIM")"
 got=$("$WORK/test_sha1_cmake" "$REPO/tests/golden/400kb.txt" 0:409600 | awk '/^hash /{print $2}')
