@@ -3,6 +3,7 @@
 
 HIPCC   ?= /opt/rocm/bin/hipcc
 CC      ?= gcc
+CXX     ?= g++
 ARCH    ?= gfx950
 OUT     := chunkio_amd/lib
 LIB     := $(OUT)/libchunkio_amd.so
@@ -11,11 +12,14 @@ BLD     := build
 INC     := -Iinclude -I$(SRC)
 
 CFLAGS   := -O3 -fPIC -Wall -Wextra -std=gnu11 $(INC)
+# crc_plan.cpp is plain C++: no offload arch and no ROCm include directory, so
+# a HIP header there fails the build.
+CXXFLAGS := -O3 -fPIC -Wall -Wextra -std=c++17 $(INC)
 HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -std=c++17 -Wall $(INC) -munsafe-fp-atomics \
             -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-kernarg-preload-count=9
 
 COBJS   := $(BLD)/host_copy.o $(BLD)/crc32_host.o $(BLD)/crc32_scalar.o $(BLD)/cio_verify.o $(BLD)/cio_sync.o $(BLD)/cioa_chunk.o $(BLD)/crc_route.o $(BLD)/crc_cpu_batch.o $(BLD)/cio_sha1.o
-HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o
+HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o
 
 CTEST   := tests/c/bin
 REF_INC := /root/reference/include/chunkio/cio_crc32.h
@@ -62,6 +66,10 @@ $(BLD)/%.o: $(SRC)/%.c $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
 	@mkdir -p $(BLD)
 	$(CC) $(CFLAGS) -c -o $@ $<
 
+$(BLD)/%.o: $(SRC)/%.cpp $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
+	@mkdir -p $(BLD)
+	$(CXX) $(CXXFLAGS) -c -o $@ $<
+
 $(BLD)/%.o: $(SRC)/%.hip $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
 	@mkdir -p $(BLD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -74,20 +82,32 @@ oracle:
 	$(MAKE) -C oracle
 
 # A/B variant of the library: make ablib VAR=name DEFS="-DFOO" -> chunkio_amd/lib/ab/name.so
+# $(DEFS) reaches every unit that reads cio_diag.h for CRC: the kernels, the
+# planner (CIO_HEAD_ALIGN in plan_build) and the runtime (cio_gpu_version).
 ablib:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/crc32_gpu_$(VAR).o $(SRC)/crc32_gpu.hip
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o -lpthread
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/gpu_runtime_$(VAR).o $(SRC)/gpu_runtime.hip
+	$(CXX) $(CXXFLAGS) $(DEFS) -c -o $(BLD)/ab/crc_plan_$(VAR).o $(SRC)/crc_plan.cpp
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o -lpthread
 
 # Same for the SHA-1 kernel: make ablib_sha1 VAR=name DEFS="-DCIO_SHA1_CHAINS=32"
 ablib_sha1:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/sha1_gpu_$(VAR).o $(SRC)/sha1_gpu.hip
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o -lpthread
 
 asm: $(SRC)/crc32_gpu.hip
 	@mkdir -p $(BLD)/asm
 	$(HIPCC) $(HIPFLAGS) --offload-device-only -S -o $(BLD)/asm/crc32_gpu.s $<
+
+# The host planner under ASan + UBSan, stand-alone (no GPU, no HIP): the
+# shipped choices over the geometries of tests/test_plan_choice.py.
+plancheck:
+	@mkdir -p $(BLD)/plancheck
+	$(CC) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=gnu11 $(INC) -c -o $(BLD)/plancheck/crc32_host.o $(SRC)/crc32_host.c
+	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/plancheck/plan_check tools/plan_check.cpp $(SRC)/crc_plan.cpp $(BLD)/plancheck/crc32_host.o -lpthread
+	$(BLD)/plancheck/plan_check
 
 # make install PREFIX=/usr/local: the library, the public headers (crc32/crc32.h,
 # sha1/sha1.h, chunkio_amd/*.h) and a pkg-config file, for a chunkio build to
@@ -107,4 +127,4 @@ clean:
 	rm -rf $(BLD) $(LIB) $(CTEST)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle asm clean ctests ablib ablib_sha1 install
+.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck install

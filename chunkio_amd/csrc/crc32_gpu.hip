@@ -1831,595 +1831,7 @@ read_stream_dyn_kernel(const uint8_t *__restrict__ base, uint64_t S, uint64_t Ss
 
 }  // namespace
 
-namespace cioa {
-
-thread_local std::string g_err;
-
-int fail(const char *what, hipError_t e)
-{
-    char buf[512];
-    if (e != hipSuccess) {
-        snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    } else {
-        snprintf(buf, sizeof(buf), "%s", what);
-    }
-    g_err = buf;
-    return CIO_ERROR;
-}
-
-}  // namespace cioa
-
-extern "C" int cioa_fail_msg(const char *what, const char *detail)
-{
-    g_err = std::string(what) + (detail ? std::string(": ") + detail : std::string());
-    return CIO_ERROR;
-}
-
-namespace cioa {
-
-// One DeviceState per HIP device, allocated once and never moved: plans and
-// in-flight host batches keep a pointer to it (a growing vector
-// here reallocated under them when a second device was first used).
-std::mutex g_mu;
-std::unique_ptr<DeviceState> g_dev[kMaxDev];
-
-int device_state(DeviceState **out)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
-    if (dev < 0 || dev >= kMaxDev) {
-        return fail("device ordinal out of range");
-    }
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_dev[dev]) {
-        g_dev[dev].reset(new DeviceState());
-    }
-    DeviceState &st = *g_dev[dev];
-    if (!st.ready) {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, dev), "hipGetDeviceProperties");
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            char msg[256];
-            snprintf(msg, sizeof(msg), "chunkio_amd kernels are built for gfx950, device is %s",
-                     prop.gcnArchName);
-            return fail(msg);
-        }
-        st.cus = prop.multiProcessorCount;
-        static uint32_t slice[4][256], shift[4][256];
-        std::vector<uint32_t> x8(kX8Count);
-        cioa_gen_slice4(slice);
-        cioa_gen_shift_table(shift, (uint64_t) (kStep - kGran));
-        cioa_gen_xpow8_table(x8.data(), kX8Count, 1);
-        HIP_TRY(hipMalloc(&st.slice, sizeof(slice)), "hipMalloc(slice)");
-        HIP_TRY(hipMalloc(&st.shift, sizeof(shift)), "hipMalloc(shift)");
-        HIP_TRY(hipMalloc(&st.x8, kX8Count * sizeof(uint32_t)), "hipMalloc(x8)");
-        HIP_TRY(hipMemcpy(st.slice, slice, sizeof(slice), hipMemcpyHostToDevice), "upload slice");
-        HIP_TRY(hipMemcpy(st.shift, shift, sizeof(shift), hipMemcpyHostToDevice), "upload shift");
-        HIP_TRY(hipMemcpy(st.x8, x8.data(), kX8Count * sizeof(uint32_t), hipMemcpyHostToDevice),
-                "upload x8");
-        // x^-1 = (P(x) - 1) / x, reflected: P's low coefficients moved down one power.
-        std::vector<uint32_t> xinv8(kStep);
-        uint32_t xm8 = 0x80000000u;
-        for (int i = 0; i < 8; ++i) {
-            xm8 = cioa_multmodp(xm8, (CIOA_POLY << 1) | 1u);
-        }
-        xinv8[0] = 0x80000000u;
-        for (int d = 1; d < kStep; ++d) {
-            xinv8[d] = cioa_multmodp(xinv8[d - 1], xm8);
-        }
-        HIP_TRY(hipMalloc(&st.xinv8, kStep * sizeof(uint32_t)), "hipMalloc(xinv8)");
-        HIP_TRY(hipMemcpy(st.xinv8, xinv8.data(), kStep * sizeof(uint32_t), hipMemcpyHostToDevice),
-                "upload xinv8");
-        st.ready = true;
-    }
-    *out = &st;
-    return CIO_OK;
-}
-
-}  // namespace cioa
-
 extern "C" {
-
-const char *cio_gpu_last_error(void)
-{
-    return g_err.c_str();
-}
-
-const char *cio_gpu_version(void)
-{
-#define CIO_STR2(x) #x
-#define CIO_STR(x) CIO_STR2(x)
-    return "chunkio_amd crc32 v9 gfx950 stream(l64-lanes permlane-transpose issue-ahead<=64steps pre-shift prio-rotate "
-           "coalesced-nt division-free-start slice4-lds32x perm direct-whole preshifted-partials wg-lds-fold "
-           "head-align=" CIO_STR(CIO_HEAD_ALIGN) ") "
-           "small(4x16B dpp-reduce bitop3-fold prio-rotate) "
-           "host(nt-staging graduated-groups pread-bounce multi-device vpclmul-crc_update small-batch-route) "
-           "sha1(2-schedule-waves 4-block-handover continuation)";
-}
-
-int cio_gpu_init(void)
-{
-    DeviceState *st;
-    return device_state(&st);
-}
-
-void cio_crc32_plan_destroy(cio_crc32_plan *p)
-{
-    if (!p) {
-        return;
-    }
-    (void) hipFree(p->desc);
-    (void) hipFree(p->wstart);
-    (void) hipFree(p->tiny);
-    (void) hipFree(p->partials);
-    (void) hipFree(p->counters);
-    (void) hipFree(p->pfac);
-    (void) hipFree(p->stamps);
-    delete p;
-}
-
-}  // extern "C"
-
-namespace cioa {
-
-// Tuning knobs (environment, read at plan creation) and grid geometry.
-void plan_init(cio_crc32_plan *p, DeviceState *st, size_t n)
-{
-    p->st = st;
-    p->n = (uint32_t) n;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_PRIO")) {
-        const int v = atoi(r);
-        p->prio = (v == 0) ? 0 : 1;
-    }
-    // Lane layout of the CRC kernels (profiles/r03/ab_l64_*.txt): the
-    // stream kernels take one 64-byte chain per lane (L64, permlane
-    // transpose: cfg2 -5 %, cfg3 -1 %, 4 MiB chunks -1 to -2.5 %); the small
-    // kernel keeps the 4-sub-chain layout (L64 there: cfg4k +1 %, 64 Ki x
-    // 4 KiB -3.5 %).  CIO_GPU_L64=1 / 0 forces one layout on both.
-    p->l64 = true;
-    p->l64_small = false;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_L64")) {
-        p->l64 = p->l64_small = atoi(r) != 0;
-    }
-    p->grid = (uint32_t) st->cus;
-    // Test / A/B knob: another workgroup count (fewer than CUs: e.g. a wave
-    // count that is not a power of two, which takes the kernels' f64 split
-    // instead of the shift; more: workgroups that queue for a CU, up to 16
-    // per CU).
-    if (const char *r = cioa_diag_getenv("CIO_GPU_GRID")) {
-        const int v = atoi(r);
-        if (v >= 1 && v <= 16 * (int) p->grid) {
-            p->grid = (uint32_t) v;
-        }
-    }
-    p->W = p->grid * (kThreads / kWave);
-}
-
-// Virtual aligned chunks, wave-step numbering, the even split of the S steps
-// over W waves, each wave's first chunk, per-chunk piece counts and per-slot
-// fold factors.  Host only; returns an error message or nullptr.
-const char *plan_build(PlanHost &ph, const uint64_t *offs, const uint64_t *lens, size_t n, uint32_t W)
-{
-    ph.desc.assign(n ? n : 1, ChunkDesc{});
-    ph.tiny.clear();
-    uint64_t S = 0, bytes = 0;
-    for (size_t i = 0; i < n; i++) {
-        ChunkDesc &d = ph.desc[i];
-        const uint64_t amask = lens[i] > (uint64_t) kStep ? (uint64_t) CIO_HEAD_ALIGN - 1 : 15ull;
-        d.a = offs[i] & ~amask;
-        d.h = (uint32_t) (offs[i] & amask);
-        d.vlen = d.h + lens[i];
-        d.g = S;
-        const uint64_t ns = lens[i] >= 4 ? (d.vlen + kStep - 1) / kStep : 0;
-        if (ns > 0xffffffffull) {
-            return "cio_crc32_plan_create: chunk too large";
-        }
-        d.nsteps = (uint32_t) ns;
-        if (ns == 0) {
-            ph.tiny.push_back((uint32_t) i);
-        }
-        S += ns;
-        bytes += lens[i];
-    }
-    // The kernels' start-up divisions (div_u52) need w * S < 2^52 for w <= W
-    // (W <= 2^12 on a full device: 2^40 wave-steps is 4 PiB, far past any
-    // device's memory).
-    if (S >= (1ull << 40) || W > 65536 || (S * (uint64_t) W) >> 52) {
-        return "cio_crc32_plan_create: batch too large";
-    }
-    ph.S = S;
-    ph.bytes = bytes;
-
-    // Fold factors x^(8 d) for d = bytes after a piece = 4096 m + r: one
-    // multiply of two table entries (x8 static, x4k per plan up to the
-    // longest chunk) instead of a square-and-multiply per piece.
-    static const std::vector<uint32_t> x8 = [] {
-        std::vector<uint32_t> t(kStep);
-        cioa_gen_xpow8_table(t.data(), kStep, 1);
-        return t;
-    }();
-    uint64_t max_steps = 0;
-    for (size_t i = 0; i < n; i++) {
-        max_steps = std::max<uint64_t>(max_steps, ph.desc[i].nsteps);
-    }
-    std::vector<uint32_t> x4k;
-    if (max_steps <= (1u << 20)) {
-        x4k.resize(max_steps + 1);
-        cioa_gen_xpow8_table(x4k.data(), x4k.size(), (uint64_t) kStep);
-    }
-    auto factor = [&](uint64_t d) {
-        const uint64_t m = d / kStep, r = d % kStep;
-        if (m == 0) {
-            return x8[r];
-        }
-        return m < x4k.size() ? cioa_multmodp(x4k[m], x8[r]) : cioa_xpow8n(d);
-    };
-
-    std::vector<uint32_t> wc(W, 0), wl(W, 0);
-    const size_t nslots = (size_t) W + n + 1;
-    ph.pfac.assign(nslots + 2 * (size_t) W, 0u);
-    if (S > 0) {
-        size_t c = 0;
-        for (uint32_t w = 0; w < W; w++) {
-            const uint64_t g0 = ((uint64_t) w * S) / W;
-            const uint64_t g1 = ((uint64_t) (w + 1) * S) / W;
-            while (c < n && (ph.desc[c].nsteps == 0 || ph.desc[c].g + ph.desc[c].nsteps <= g0)) {
-                c++;
-            }
-            wc[w] = (uint32_t) std::min(c, n - 1);
-            if (g0 == g1) {
-                continue;
-            }
-            for (size_t k = c; k < n && ph.desc[k].g < g1; k++) {
-                ChunkDesc &d = ph.desc[k];
-                if (d.nsteps) {
-                    if (d.npieces == 0) {
-                        d.w0 = w;
-                    }
-                    d.w1 = w;
-                    wl[w] = (uint32_t) k;
-                    d.npieces++;
-                    const uint64_t pend = std::min(std::min(g1 - d.g, (uint64_t) d.nsteps) * (uint64_t) kStep,
-                                                   d.vlen);
-                    ph.pfac[w + k] = factor(d.vlen - pend);
-                }
-            }
-        }
-    }
-    // Workgroup-local chunks: split, with every piece in one workgroup.
-    auto local = [](const ChunkDesc &d) {
-        return d.npieces > 1 && d.w0 / kWavesPerWg == d.w1 / kWavesPerWg;
-    };
-    for (uint32_t w = 0; S > 0 && w < W; w++) {
-        const uint64_t g0 = ((uint64_t) w * S) / W;
-        const uint64_t g1 = ((uint64_t) (w + 1) * S) / W;
-        if (g0 == g1) {
-            continue;
-        }
-        uint32_t f = 0;
-        const ChunkDesc &first = ph.desc[wc[w]];
-        if (first.g < g0 && first.g + first.nsteps <= g1 && local(first)) {
-            f |= kWfFold | ((w - first.w0) << 8);
-        }
-        const ChunkDesc &last = ph.desc[wl[w]];
-        const bool nonfinal = last.g + last.nsteps > g1;
-        if (nonfinal && local(last)) {
-            f |= kWfPublish;
-        }
-        ph.pfac[nslots + w] = f;
-        // The last piece's factor (x^0 = 0x80000000 when it ends its chunk).
-        ph.pfac[nslots + W + w] = nonfinal ? ph.pfac[w + wl[w]] : 0x80000000u;
-    }
-    ph.ws.assign(W, WaveStart{});
-    for (uint32_t w = 0; w < W; w++) {
-        ph.ws[w].c = wc[w];
-        if (n) {
-            ph.ws[w].d = ph.desc[wc[w]];
-        }
-    }
-    return nullptr;
-}
-
-}  // namespace cioa
-
-namespace {
-
-// Uniform batch: n equal lengths >= 4 at offsets off0 + i * stride with
-// stride a multiple of 16 (every chunk has the same misalignment).  The
-// kernel then derives chunk descriptors arithmetically (CIO_GPU_UNIFORM=0
-// disables).
-void plan_uniform(cio_crc32_plan *p, const uint64_t *offs, const uint64_t *lens, size_t n, const PlanHost &ph)
-{
-    p->unsteps = 0;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_UNIFORM")) {
-        if (!atoi(r)) {
-            return;
-        }
-    }
-    if (n == 0 || lens[0] < 4 || ph.desc[0].nsteps == 0) {
-        return;
-    }
-    const uint64_t stride = n > 1 ? offs[1] - offs[0] : 0;
-    if (n > 1 && (offs[1] < offs[0] || (stride & 15) != 0)) {
-        return;
-    }
-    for (size_t i = 1; i < n; i++) {
-        if (lens[i] != lens[0] || offs[i] != offs[0] + i * stride || ph.desc[i].h != ph.desc[0].h) {
-            return;
-        }
-    }
-    p->ustride = stride;
-    p->ua0 = ph.desc[0].a;
-    p->uvlen = ph.desc[0].vlen;
-    p->uh = ph.desc[0].h;
-    p->unsteps = ph.desc[0].nsteps;
-}
-
-}  // namespace
-
-extern "C" {
-
-int cio_crc32_plan_create(cio_crc32_plan **out, const uint64_t *offs, const uint64_t *lens, size_t n)
-{
-    if (!out || (n && (!offs || !lens))) {
-        return fail("cio_crc32_plan_create: null argument");
-    }
-    if (n >= 0xffffffffull) {
-        return fail("cio_crc32_plan_create: too many chunks");
-    }
-    *out = nullptr;
-    DeviceState *st;
-    if (device_state(&st) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    cio_crc32_plan *p = new cio_crc32_plan();
-    plan_init(p, st, n);
-    PlanHost ph;
-    if (const char *err = plan_build(ph, offs, lens, n, p->W)) {
-        delete p;
-        return fail(err);
-    }
-    plan_uniform(p, offs, lens, n, ph);
-    // Long batches (>= 4 MiB per wave: cfg3's ~2400 steps per wave, cfg4's
-    // 2048 at one GPU) split over 4 workgroups per CU: the extra workgroups
-    // queue for a CU and start wherever one finishes, so the hardware evens
-    // out the per-CU finish times (cfg3 -0.7 %, cfg4 -1.7 %; shorter ranges
-    // lose: 1 MiB per wave +0.8 to +5.5 %, cfg2 +5 %:
-    // profiles/r04/ab_grid_oversubscribed_r04q.txt, ab_grid_cfg4_r04x.txt).
-    bool oversub = false;
-    if (!cioa_diag_getenv("CIO_GPU_GRID") && ph.S >= 1024ull * p->W && 4ull * p->W <= 65536 &&
-        ph.S != (uint64_t) n - ph.tiny.size()) {    // (not a small-chunk batch)
-        PlanHost ph4;
-        if (plan_build(ph4, offs, lens, n, 4 * p->W) == nullptr) {
-            p->grid *= 4;
-            p->W *= 4;
-            oversub = true;
-            ph = std::move(ph4);
-        }
-    }
-    // HBM channel camping (profiles/r05/camping/): when every wave's range is
-    // the same multiple of 16 steps (64 KiB), all waves read addresses equal
-    // modulo 64 KiB at the same moment and even the read-only stream loses
-    // 5-10 % (16, 32, 64 steps per wave against 17, 33, 65).  One workgroup
-    // fewer per 32 -- one per XCD, so the XCDs stay balanced -- makes the
-    // ranges uneven and breaks the congruence.  Warm ABBA A/B
-    // (ab_anticamp_abba_r05x.txt): stream kernel +4.1 to +4.6 % at 16-64
-    // steps per wave, -1.0 % at 128 and 256; small-chunk kernel +10.9 to
-    // +14.3 % at 16-64 chunks per wave, +3.9 % at 128.  CIO_GPU_ANTICAMP=0
-    // keeps the full grid; CIO_GPU_ANTICAMP_MAX overrides the range cap.
-    {
-        const char *r = cioa_diag_getenv("CIO_GPU_ANTICAMP");
-        const bool on = !(r && atoi(r) == 0);
-        const char *mx = cioa_diag_getenv("CIO_GPU_ANTICAMP_MAX");     // A/B: longest range it applies to
-        const bool small_batch = ph.S > 0 && ph.S == (uint64_t) n - ph.tiny.size();
-        const uint64_t wmax = mx ? strtoull(mx, nullptr, 10) : small_batch ? 128 : 64;
-        const uint64_t w = p->W ? ph.S / p->W : 0;
-        const bool any_grid = r && atoi(r) == 2;            // A/B: also on oversubscribed grids
-        if (on && (!oversub || any_grid) && !cioa_diag_getenv("CIO_GPU_GRID") && p->grid % 32 == 0 && ph.S % p->W == 0 &&
-            w % 16 == 0 &&
-            w > 0 && w <= wmax) {
-            const uint32_t g2 = p->grid / 32 * 31;
-            PlanHost ph2;
-            if (plan_build(ph2, offs, lens, n, g2 * (kThreads / kWave)) == nullptr) {
-                p->grid = g2;
-                p->W = g2 * (kThreads / kWave);
-                ph = std::move(ph2);
-            }
-        }
-    }
-    p->S = ph.S;
-    p->bytes = ph.bytes;
-    p->ntiny = (uint32_t) ph.tiny.size();
-    // Uniform batch of whole 4 KiB steps, 16-byte aligned, with short wave
-    // ranges (<= 64 steps, e.g. cfg2's 25): the issue-ahead stream kernel.
-    // Interleaved A/Bs (profiles/r03/ab_issue_ahead_*.txt): cfg2 -0.6 to
-    // -1.8 %, 100- and 256-step ranges -0.3 to +0.6 % (neutral), so only
-    // short ranges, where the first steps' start-up is a larger share, take
-    // it.  CIO_GPU_AHEAD=1 forces it for any uniform aligned batch, 0 never.
-    p->ahead = p->unsteps != 0 && p->uh == 0 && p->uvlen % kStep == 0;
-    bool short_ranges = p->S <= 64ull * p->W;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_AHEAD")) {
-        short_ranges = atoi(r) != 0;
-    }
-    p->ahead = p->ahead && short_ranges;
-
-    // All chunks within one wave-step (S = number of non-tiny chunks): the
-    // small-chunk kernel (CIO_GPU_SMALL=0 disables).
-    p->small = ph.S > 0 && ph.S == (uint64_t) n - ph.tiny.size();
-    if (const char *r = cioa_diag_getenv("CIO_GPU_SMALL")) {
-        p->small = p->small && atoi(r) != 0;
-    }
-    if (const char *r = cioa_diag_getenv("CIO_GPU_STAMPS")) {
-        if (atoi(r) > 0 && hipMalloc(&p->stamps, (size_t) p->W * kStampWords * sizeof(unsigned long long)) != hipSuccess) {
-            p->stamps = nullptr;
-        }
-    }
-    hipError_t e;
-    const size_t npart = ph.pfac.size();
-    if ((e = hipMalloc(&p->desc, ph.desc.size() * sizeof(ChunkDesc))) != hipSuccess ||
-        (e = hipMalloc(&p->wstart, ph.ws.size() * sizeof(WaveStart))) != hipSuccess ||
-        (e = hipMalloc(&p->tiny, std::max<size_t>(1, ph.tiny.size()) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc(&p->partials, npart * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMalloc(&p->counters, std::max<size_t>(1, n) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc(&p->pfac, npart * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemcpy(p->desc, ph.desc.data(), ph.desc.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->wstart, ph.ws.data(), ph.ws.size() * sizeof(WaveStart), hipMemcpyHostToDevice)) != hipSuccess ||
-        (ph.tiny.size() && (e = hipMemcpy(p->tiny, ph.tiny.data(), ph.tiny.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) ||
-        (e = hipMemset(p->partials, 0, npart * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(p->counters, 0, std::max<size_t>(1, n) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemcpy(p->pfac, ph.pfac.data(), npart * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) {
-        cio_crc32_plan_destroy(p);
-        return fail("cio_crc32_plan_create: device allocation/upload", e);
-    }
-    *out = p;
-    return CIO_OK;
-}
-
-/* A ring of `depth` plans of one geometry, each on its own stream (see the
- * header): consecutive batches overlap at their kernel edges. */
-struct cio_crc32_ring {
-    std::vector<cio_crc32_plan *> plans;
-    std::vector<hipStream_t> streams;
-    std::vector<hipEvent_t> ready, done;    // per slot: caller's inputs, slot's last batch
-    std::vector<bool> pending;              // slot has work the caller has not joined
-    unsigned next = 0;
-    int dev = 0;                            // device the plans and streams live on
-};
-
-// Makes `dev` current for one scope and restores the caller's device after:
-// a ring's plans, streams and events belong to the device current at create.
-struct RingDevice {
-    int prev = -1;
-    hipError_t e = hipSuccess;
-    explicit RingDevice(int dev)
-    {
-        if ((e = hipGetDevice(&prev)) == hipSuccess && prev != dev) {
-            e = hipSetDevice(dev);
-        }
-    }
-    ~RingDevice()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) {
-            (void) hipSetDevice(prev);
-        }
-    }
-};
-
-void cio_crc32_ring_destroy(cio_crc32_ring *r)
-{
-    if (!r) {
-        return;
-    }
-    RingDevice on(r->dev);
-    for (hipStream_t st : r->streams) {
-        if (st) (void) hipStreamSynchronize(st);
-    }
-    for (size_t i = 0; i < r->plans.size(); i++) {
-        cio_crc32_plan_destroy(r->plans[i]);
-        if (r->ready[i]) (void) hipEventDestroy(r->ready[i]);
-        if (r->done[i]) (void) hipEventDestroy(r->done[i]);
-        if (r->streams[i]) (void) hipStreamDestroy(r->streams[i]);
-    }
-    delete r;
-}
-
-int cio_crc32_ring_create(cio_crc32_ring **out, const uint64_t *offs, const uint64_t *lens, size_t n, int depth)
-{
-    if (!out) {
-        return fail("cio_crc32_ring_create: null argument");
-    }
-    *out = nullptr;
-    if (depth < 1 || depth > 8) {
-        return fail("cio_crc32_ring_create: depth must be 1..8");
-    }
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev), "cio_crc32_ring_create: hipGetDevice");
-    cio_crc32_ring *r = new cio_crc32_ring();
-    r->dev = dev;
-    r->plans.assign((size_t) depth, nullptr);
-    r->streams.assign((size_t) depth, nullptr);
-    r->ready.assign((size_t) depth, nullptr);
-    r->done.assign((size_t) depth, nullptr);
-    r->pending.assign((size_t) depth, false);
-    for (int i = 0; i < depth; i++) {
-        if (cio_crc32_plan_create(&r->plans[(size_t) i], offs, lens, n) != CIO_OK) {
-            cio_crc32_ring_destroy(r);
-            return CIO_ERROR;    // (the plan's message stands)
-        }
-        hipError_t e = hipStreamCreateWithFlags(&r->streams[(size_t) i], hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ready[(size_t) i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done[(size_t) i], hipEventDisableTiming);
-        if (e != hipSuccess) {
-            cio_crc32_ring_destroy(r);
-            return fail("cio_crc32_ring_create", e);
-        }
-    }
-    *out = r;
-    return CIO_OK;
-}
-
-int cio_crc32_ring_exec(cio_crc32_ring *r, const void *dev_base, const uint32_t *dev_seeds, uint32_t *dev_out,
-                        void *stream)
-{
-    if (!r) {
-        return fail("cio_crc32_ring_exec: null ring");
-    }
-    RingDevice on(r->dev);
-    HIP_TRY(on.e, "cio_crc32_ring_exec: hipSetDevice");
-    const size_t i = r->next % r->plans.size();
-    const hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
-    // the batch waits for everything the caller queued before it (its inputs);
-    // the slot's stream orders it after the slot's previous batch (scratch reuse)
-    HIP_TRY(hipEventRecord(r->ready[i], caller), "cio_crc32_ring_exec: hipEventRecord");
-    HIP_TRY(hipStreamWaitEvent(r->streams[i], r->ready[i], 0), "cio_crc32_ring_exec: hipStreamWaitEvent");
-    if (plan_exec_impl(r->plans[i], dev_base, dev_seeds, dev_out, nullptr, r->streams[i]) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    HIP_TRY(hipEventRecord(r->done[i], r->streams[i]), "cio_crc32_ring_exec: hipEventRecord");
-    r->pending[i] = true;
-    r->next++;      // only a batch that was queued moves the ring on
-    return CIO_OK;
-}
-
-int cio_crc32_ring_join(cio_crc32_ring *r, void *stream)
-{
-    if (!r) {
-        return fail("cio_crc32_ring_join: null ring");
-    }
-    RingDevice on(r->dev);
-    HIP_TRY(on.e, "cio_crc32_ring_join: hipSetDevice");
-    const hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
-    for (size_t i = 0; i < r->plans.size(); i++) {
-        if (r->pending[i]) {
-            HIP_TRY(hipStreamWaitEvent(caller, r->done[i], 0), "cio_crc32_ring_join: hipStreamWaitEvent");
-            r->pending[i] = false;
-        }
-    }
-    return CIO_OK;
-}
-
-/* Test hook (not in the public header; host only, no device): the plan's
- * work split for W waves.  Per chunk: w0, w1, npieces (3 words); per wave:
- * the LDS-fold flags.  Returns 0, or -1 on a plan error. */
-int cioa_debug_plan_layout(const uint64_t *offs, const uint64_t *lens, size_t n, uint32_t W,
-                           uint32_t *chunk_words, uint32_t *wave_flags)
-{
-    PlanHost ph;
-    if (plan_build(ph, offs, lens, n, W) != nullptr) {
-        return -1;
-    }
-    for (size_t i = 0; i < n; i++) {
-        chunk_words[3 * i + 0] = ph.desc[i].w0;
-        chunk_words[3 * i + 1] = ph.desc[i].w1;
-        chunk_words[3 * i + 2] = ph.desc[i].npieces;
-    }
-    const size_t nslots = (size_t) W + n + 1;
-    for (uint32_t w = 0; w < W; w++) {
-        wave_flags[w] = ph.pfac[nslots + w];
-    }
-    return 0;
-}
 
 /* Diagnostic (not in the public header): copy the per-wave timestamps of the
  * last launch of a CIO_GPU_STAMPS=1 plan; returns the number of waves. */
@@ -2433,39 +1845,6 @@ int cioa_debug_stamps(const cio_crc32_plan *p, unsigned long long *host, size_t 
         return 0;
     }
     return (int) p->W;
-}
-
-uint64_t cio_crc32_plan_bytes(const cio_crc32_plan *p)
-{
-    return p ? p->bytes : 0;
-}
-
-uint32_t cio_crc32_plan_workgroups(const cio_crc32_plan *p)
-{
-    return p ? p->grid : 0;
-}
-
-const char *cio_crc32_plan_kernel(const cio_crc32_plan *p)
-{
-    return (p && p->small) ? "crc32_small_kernel" : "crc32_stream_kernel";
-}
-
-
-int cio_crc32_plan_exec_events(const cio_crc32_plan *p, const void *dev_base,
-                               const uint32_t *dev_seeds, uint32_t *dev_out, void *stream,
-                               void *ev_piece_start, void *ev_piece_stop)
-{
-    return plan_exec_impl(p, dev_base, dev_seeds, dev_out, nullptr,
-                          reinterpret_cast<hipStream_t>(stream),
-                          reinterpret_cast<hipEvent_t>(ev_piece_start),
-                          reinterpret_cast<hipEvent_t>(ev_piece_stop));
-}
-
-int cio_crc32_plan_exec(const cio_crc32_plan *p, const void *dev_base, const uint32_t *dev_seeds,
-                        uint32_t *dev_out, void *stream)
-{
-    return plan_exec_impl(p, dev_base, dev_seeds, dev_out, nullptr,
-                          reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
@@ -2578,24 +1957,6 @@ int cioa::devplan_crc_launch(const cio_crc32_plan *p, const unsigned long long *
 }
 
 extern "C" {
-
-int cio_crc32_batch_dev(const void *dev_base, const uint64_t *offs, const uint64_t *lens,
-                        const uint32_t *dev_seeds, uint32_t *dev_out, size_t n, void *stream)
-{
-    cio_crc32_plan *p = nullptr;
-    if (cio_crc32_plan_create(&p, offs, lens, n) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    int rc = cio_crc32_plan_exec(p, dev_base, dev_seeds, dev_out, stream);
-    if (rc == CIO_OK) {
-        hipError_t e = hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream));
-        if (e != hipSuccess) {
-            rc = fail("cio_crc32_batch_dev: stream sync", e);
-        }
-    }
-    cio_crc32_plan_destroy(p);
-    return rc;
-}
 
 int cio_gpu_fill_synthetic(void *dev_base, const uint64_t *offs, const uint64_t *lens,
                            const uint64_t *ids, size_t n, uint64_t seed, void *stream)
@@ -2756,48 +2117,6 @@ static int read_stream_impl(const void *dev_base, uint64_t bytes, void *stream, 
     if (ev1) {
         HIP_TRY(hipEventRecord(ev1, reinterpret_cast<hipStream_t>(stream)), "hipEventRecord");
     }
-    return CIO_OK;
-}
-
-void *cio_gpu_event_create(void)
-{
-    hipEvent_t ev = nullptr;
-    if (hipEventCreate(&ev) != hipSuccess) {
-        return nullptr;
-    }
-    return ev;
-}
-
-void cio_gpu_event_destroy(void *ev)
-{
-    if (ev) {
-        (void) hipEventDestroy(reinterpret_cast<hipEvent_t>(ev));
-    }
-}
-
-int cio_gpu_event_record(void *ev, void *stream)
-{
-    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(ev), reinterpret_cast<hipStream_t>(stream)),
-            "hipEventRecord");
-    return CIO_OK;
-}
-
-float cio_gpu_event_elapsed_ms(void *start, void *stop)
-{
-    float ms = -1.0f;
-    if (hipEventSynchronize(reinterpret_cast<hipEvent_t>(stop)) != hipSuccess) {
-        return -1.0f;
-    }
-    if (hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(start),
-                            reinterpret_cast<hipEvent_t>(stop)) != hipSuccess) {
-        return -1.0f;
-    }
-    return ms;
-}
-
-int cio_gpu_stream_sync(void *stream)
-{
-    HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)), "hipStreamSynchronize");
     return CIO_OK;
 }
 

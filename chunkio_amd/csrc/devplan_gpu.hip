@@ -4,7 +4,7 @@
 // include/chunkio_amd/cio_verify.h (cio_file_verify_batch_dev).
 //
 // cio_crc32_plan_create builds the stream kernel's work partition on the host
-// (cioa::plan_build, crc32_gpu.hip) from HOST offsets and lengths.  Here the
+// (cioa::plan_build, crc_plan.cpp) from HOST offsets and lengths.  Here the
 // same partition -- byte for byte -- is written by four small kernels from
 // offsets and lengths that live in device memory, so a batch whose geometry
 // the host never sees (a length read from a chunk header in HBM, a captured
@@ -663,28 +663,6 @@ int cioa_debug_devplan_image(cio_crc32_devplan *dp, uint64_t dev_bytes, const ui
     if (pfac) HIP_TRY(hipMemcpy(pfac, p->pfac, (W + n + 1 + 2 * W) * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy pfac");
     if (hdr) HIP_TRY(hipMemcpy(hdr, dp->hdr, kDevHdrWords * sizeof(uint64_t), hipMemcpyDeviceToHost), "copy header");
     return CIO_OK;
-}
-
-/* Its host twin (no device): plan_build's arrays for the same inputs and W,
- * in the same layout; hdr = {S, ntiny, bytes, 0}.  -1 on a plan error. */
-int cioa_debug_plan_image(const uint64_t *offs, const uint64_t *lens, size_t n, uint32_t W, void *desc,
-                          void *wstart, uint32_t *tiny, uint32_t *pfac, uint64_t *hdr)
-{
-    PlanHost ph;
-    if (plan_build(ph, offs, lens, n, W) != nullptr) {
-        return -1;
-    }
-    memcpy(desc, ph.desc.data(), n * sizeof(ChunkDesc));
-    memcpy(wstart, ph.ws.data(), (size_t) W * sizeof(WaveStart));
-    if (!ph.tiny.empty()) {
-        memcpy(tiny, ph.tiny.data(), ph.tiny.size() * sizeof(uint32_t));
-    }
-    memcpy(pfac, ph.pfac.data(), ph.pfac.size() * sizeof(uint32_t));
-    hdr[kDevHdrS] = ph.S;
-    hdr[kDevHdrNtiny] = ph.tiny.size();
-    hdr[kDevHdrBytes] = ph.bytes;
-    hdr[kDevHdrStatus] = 0;
-    return 0;
 }
 
 }  // extern "C"

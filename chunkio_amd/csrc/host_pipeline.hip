@@ -1,6 +1,6 @@
 // host_pipeline.hip -- the batch path for chunks in host memory or in files
 // (cio_crc32_batch_host[_multi], cio_crc32_batch_fd_multi, registered ranges,
-// device selection).  Kernels, plans and device state: crc32_gpu.hip.
+// device selection).  Kernels: crc32_gpu.hip; plans and device state: crc_plan.cpp, gpu_runtime.hip.
 #include <stdint.h>
 #include <string.h>
 #include <stdio.h>
