@@ -19,7 +19,7 @@ HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -std=c++17 -Wall $(INC) -munsafe-fp
             -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-kernarg-preload-count=9
 
 COBJS   := $(BLD)/host_copy.o $(BLD)/crc32_host.o $(BLD)/crc32_scalar.o $(BLD)/cio_verify.o $(BLD)/cio_sync.o $(BLD)/cioa_chunk.o $(BLD)/crc_route.o $(BLD)/crc_cpu_batch.o $(BLD)/cio_sha1.o
-HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o
+HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o
 
 CTEST   := tests/c/bin
 REF_INC := /root/reference/include/chunkio/cio_crc32.h
@@ -89,13 +89,13 @@ ablib:
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/crc32_gpu_$(VAR).o $(SRC)/crc32_gpu.hip
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/gpu_runtime_$(VAR).o $(SRC)/gpu_runtime.hip
 	$(CXX) $(CXXFLAGS) $(DEFS) -c -o $(BLD)/ab/crc_plan_$(VAR).o $(SRC)/crc_plan.cpp
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o -lpthread
 
 # Same for the SHA-1 kernel: make ablib_sha1 VAR=name DEFS="-DCIO_SHA1_CHAINS=32"
 ablib_sha1:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/sha1_gpu_$(VAR).o $(SRC)/sha1_gpu.hip
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o -lpthread
 
 asm: $(SRC)/crc32_gpu.hip
 	@mkdir -p $(BLD)/asm
@@ -108,6 +108,13 @@ plancheck:
 	$(CC) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=gnu11 $(INC) -c -o $(BLD)/plancheck/crc32_host.o $(SRC)/crc32_host.c
 	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/plancheck/plan_check tools/plan_check.cpp $(SRC)/crc_plan.cpp $(BLD)/plancheck/crc32_host.o -lpthread
 	$(BLD)/plancheck/plan_check
+
+# The append copy's partition and unit arithmetic (write_dev_copy.h, the text
+# the device kernel runs) under ASan + UBSan, stand-alone (no GPU, no HIP).
+copycheck:
+	@mkdir -p $(BLD)/copycheck
+	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/copycheck/copy_check tools/copy_check.cpp
+	$(BLD)/copycheck/copy_check
 
 # make install PREFIX=/usr/local: the library, the public headers (crc32/crc32.h,
 # sha1/sha1.h, chunkio_amd/*.h) and a pkg-config file, for a chunkio build to
@@ -127,4 +134,4 @@ clean:
 	rm -rf $(BLD) $(LIB) $(CTEST)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck install
+.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck copycheck install

@@ -9,7 +9,9 @@ Layers:
                                                    OpenSSL-layout SHA_CTX bytes)
   chunkio_amd/chunkfile.py                         binding of the C chunk layer
                                                    (cioa_chunk.h: write/sync/verify/tx/scan,
-                                                   up_batch)
+                                                   up_batch) and of the device-side write
+                                                   path (cio_write_dev.h: DevWriter,
+                                                   init / write / seal_batch_dev)
 """
 from ._lib import LIB_PATH, CioGpuError, lib  # noqa: F401
 from .crc32 import (  # noqa: F401
@@ -20,6 +22,8 @@ from .crc32 import (  # noqa: F401
     sha1_states_init, sha1_states_view, sha1_update_batch_dev,
 )
 
-from .chunkfile import verify_batch_dev  # noqa: F401,E402
+from .chunkfile import (  # noqa: F401,E402
+    CIOA_SEAL_RECOMPUTE, DevWriter, init_batch_dev, seal_batch_dev, verify_batch_dev, write_batch_dev,
+)
 
 __version__ = "0.5.0"

@@ -23,6 +23,12 @@ the stream dirname(path).
 
 verify_paths(paths) is the batched verify-on-load of a list of chunk files
 (cio_verify_paths_multi).
+
+DevWriter with init_batch_dev / write_batch_dev / seal_batch_dev is the write
+lifecycle of chunk images that live in device memory
+(include/chunkio_amd/cio_write_dev.h): write_init_header, cio_file_write +
+update_checksum and finalize_checksum (src/cio_file.c:149-162, 994-1073,
+97-124) in batches, on cuda tensors, without waiting.
 """
 import ctypes
 import os
@@ -41,6 +47,7 @@ CIO_ERR_BAD_CHECKSUM, CIO_ERR_BAD_LAYOUT, CIO_ERR_PERMISSION, CIO_ERR_BAD_FILE_S
 CIOA_VERIFY_DELETE_IRRECOVERABLE = 16
 CIOA_VERIFY_WRITEBACK = 64
 CIOA_SYNC_FINALIZE, CIOA_SYNC_MSYNC, CIOA_SYNC_FULL = 1, 2, 8
+CIOA_SEAL_RECOMPUTE = 256
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -176,6 +183,99 @@ def verify_batch_dev(plan, base, img_offs, img_sizes, flags=CIO_CHECKSUM, stream
                                               _ptr(cr), _ptr(ml), _ptr(cl), _stream_ptr(stream))
     _lib.check(rc, "cio_file_verify_batch_dev")
     return st[:n], er[:n], cr[:n], ml[:n], cl[:n]
+
+
+class DevWriter:
+    """A writer of chunk images in device memory (cio_dev_writer_*): a device
+    plan and arenas for batches of up to max_chunks images.  Not thread-safe;
+    one call in flight at a time."""
+
+    def __init__(self, max_chunks):
+        self.max_chunks = int(max_chunks)
+        handle = ctypes.c_void_p()
+        _lib.check(_lib.lib().cio_dev_writer_create(ctypes.byref(handle), self.max_chunks),
+                   "cio_dev_writer_create")
+        self._handle = handle
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            _lib.lib().cio_dev_writer_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _status_out(status, n, dev):
+    import torch
+    if status is None:
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    return status
+
+
+def init_batch_dev(writer, base, img_offs, img_caps, meta_src=None, meta_offs=None, meta_lens=None,
+                   flags=CIO_CHECKSUM, crc_cur=None, status=None, stream=None):
+    """Initialise chunk images in device memory (cio_file_init_batch_dev):
+    image i is base[img_offs[i]:img_offs[i] + img_caps[i]].  With meta_src (uint8
+    cuda tensor) record i of it, meta_src[meta_offs[i]:+meta_lens[i]], becomes
+    the image's metadata.  base: uint8 cuda tensor; offsets, capacities and
+    lengths: 64-bit cuda tensors.  Queues the work on `stream` and returns
+    (status int32, crc_cur int32 holding the uint32 bits) cuda tensors without
+    waiting; crc_cur / status may be passed in to be reused."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    if crc_cur is None:
+        crc_cur = torch.zeros(max(n, 1), dtype=torch.int32, device=base.device)
+    rc = _lib.lib().cio_file_init_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n,
+        _ptr(meta_src), 0 if meta_src is None else meta_src.numel() * meta_src.element_size(),
+        _ptr(meta_offs), _ptr(meta_lens), int(flags), _ptr(crc_cur), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_init_batch_dev")
+    return status[:n], crc_cur[:n]
+
+
+def write_batch_dev(writer, base, img_offs, img_caps, src, src_offs, src_lens, crc_cur, flags=CIO_CHECKSUM,
+                    status=None, stream=None):
+    """Append record i, src[src_offs[i]:+src_lens[i]], to image i
+    (cio_file_write_batch_dev); crc_cur (int32 cuda tensor of n, from
+    init_batch_dev) is updated in place when flags has CIO_CHECKSUM.  The
+    content lengths are read from the images on the device, so a captured call
+    appends again on every replay.  Returns the status cuda tensor (int32)
+    without waiting; pass `status` to reuse one (under graph capture)."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_write_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n,
+        _ptr(src), src.numel() * src.element_size(), _ptr(src_offs), _ptr(src_lens), int(flags), _ptr(crc_cur),
+        _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_write_batch_dev")
+    return status[:n]
+
+
+def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM, status=None, stream=None):
+    """Seal the images (cio_file_seal_batch_dev): the finalized CRC goes into
+    bytes 2..9; with CIOA_SEAL_RECOMPUTE crc_cur is first recomputed from the
+    image.  Returns the status cuda tensor (int32) without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_seal_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n,
+        int(flags), _ptr(crc_cur), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_seal_batch_dev")
+    return status[:n]
 
 
 class Context:

@@ -1,0 +1,543 @@
+// write_dev_gpu.hip -- chunkio's write lifecycle for chunk images in HBM, for
+// CDNA4 (gfx950, MI355X): initialise, append, seal.  C ABI in
+// include/chunkio_amd/cio_write_dev.h; DESIGN.md §14.
+//
+// An append batch is a serial chain of kernels on the caller's stream:
+//
+//   write_headers  one thread per image: the checks, and -- into the writer's
+//                  arenas -- the record's validated source region, its
+//                  destination offset and the new content length.  A rejected
+//                  entry gets a zero-length region, so the batch keeps its
+//                  indexing and nothing of that entry is copied or CRC'd.
+//   planner        devplan's four kernels over the source regions.  They run
+//                  for the CRC anyway; desc[i].g / nsteps is the exclusive
+//                  scan of the records' 4 KiB steps, which is exactly the
+//                  byte-balanced partition the copy needs, so the copy reads
+//                  it instead of running a scan of its own.
+//   append_copy    the hot path: every wave takes an even share of the S
+//                  steps, whatever records they belong to.
+//   CRC            the device-planned stream kernel over the SOURCE records,
+//                  seeds = crc_cur, output in writer scratch (not in place).
+//   write_finish   one thread per image: crc_cur, bytes 2..9, bytes 10..13.
+//
+// Init is the same chain over the metadata records (seed = the CRC state after
+// the two length bytes, computed per thread); seal with CIOA_SEAL_RECOMPUTE is
+// verify-on-load's chain (header kernel, planner + CRC over the image regions)
+// with a finish kernel that stores instead of comparing.
+//
+// The layout (cio_layout.h holds it for the host) restated for the device:
+//   0..1 magic C1 00 | 2..9 CRC (8-byte crc_t) | 10..13 content length BE
+//   22..23 metadata length BE | 24.. metadata, then content.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "cio_gpu_internal.h"
+#include "write_dev_copy.h"
+#include "chunkio_amd/cio_write_dev.h"
+
+using namespace cioa;
+
+namespace {
+
+constexpr uint32_t kHdrMin = 24;
+constexpr uint32_t kCopyThreads = 256;                 // 4 waves per workgroup
+constexpr uint32_t kCopyWaves = kCopyThreads / kWave;
+constexpr uint32_t kCopyWgPerCu = 8;                   // 32 waves per CU in flight
+constexpr uint64_t kMaxContent = 0xffffffffull;        // the length field is 32 bits
+
+__device__ __forceinline__ uint32_t be32(const uint8_t *p)
+{
+    return ((uint32_t) p[0] << 24) | ((uint32_t) p[1] << 16) | ((uint32_t) p[2] << 8) | p[3];
+}
+
+__device__ __forceinline__ void put_be32(uint8_t *p, uint32_t v)
+{
+    p[0] = (uint8_t) (v >> 24);
+    p[1] = (uint8_t) (v >> 16);
+    p[2] = (uint8_t) (v >> 8);
+    p[3] = (uint8_t) v;
+}
+
+// crc_update over one byte, bit by bit (raw state, reflected polynomial).
+__device__ __forceinline__ uint32_t crc_byte(uint32_t crc, uint32_t b)
+{
+    crc ^= b;
+    for (int k = 0; k < 8; ++k) {
+        crc = (crc >> 1) ^ (CIOA_POLY & (0u - (crc & 1u)));
+    }
+    return crc;
+}
+
+__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
+{
+    return off + len >= off && off + len <= bytes;
+}
+
+// The image checks shared by write and seal: inside dev_bytes, room for a
+// header, the magic, and metadata + content inside the capacity.
+__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap,
+                                         uint32_t &meta, uint64_t &content)
+{
+    if (!range_ok(off, cap, dev_bytes) || cap < kHdrMin) {
+        return false;
+    }
+    const uint8_t *p = base + off;
+    if (p[0] != 0xc1 || p[1] != 0x00) {
+        return false;
+    }
+    meta = ((uint32_t) p[22] << 8) | p[23];
+    content = be32(p + 10);
+    return (uint64_t) kHdrMin + meta + content <= cap;
+}
+
+// ---------------------------------------------------------------- init
+
+__global__ void __launch_bounds__(256)
+init_headers(uint64_t dev_bytes, const uint64_t *__restrict__ img_offs, const uint64_t *__restrict__ img_caps,
+             uint32_t n, const uint64_t *__restrict__ meta_offs, const uint64_t *__restrict__ meta_lens,
+             uint64_t meta_src_bytes, int32_t *__restrict__ status, uint64_t *__restrict__ soff,
+             uint64_t *__restrict__ slen, uint64_t *__restrict__ dst, uint32_t *__restrict__ seed)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint64_t off = img_offs[i], cap = img_caps[i];
+    const uint64_t moff = meta_offs ? meta_offs[i] : 0, m = meta_lens ? meta_lens[i] : 0;
+    bool ok = range_ok(off, cap, dev_bytes) && cap >= kHdrMin;
+    if (ok && m != 0) {
+        ok = m <= 65535u && kHdrMin + m <= cap && range_ok(moff, m, meta_src_bytes);
+    }
+    status[i] = ok ? CIO_OK : CIO_ERROR;
+    soff[i] = ok && m ? moff : 0;
+    slen[i] = ok ? m : 0;
+    dst[i] = ok ? off + kHdrMin : 0;
+    // crc_update(crc_init(), bytes 22..23): 0xBE26ED00 without metadata
+    seed[i] = crc_byte(crc_byte(0xffffffffu, (uint32_t) (m >> 8) & 0xffu), (uint32_t) m & 0xffu);
+}
+
+// crc: the CRC launch's output over the metadata, or NULL when there was none
+// (then the seed is already the state); hdr: the planner's header, or NULL
+// when no planner ran.
+__global__ void __launch_bounds__(256)
+init_finish(uint8_t *base, const uint64_t *__restrict__ img_offs, uint32_t n, int32_t *__restrict__ status,
+            const uint64_t *__restrict__ slen, const uint32_t *__restrict__ seed, const uint32_t *__restrict__ crc,
+            const unsigned long long *__restrict__ hdr, int checksum, uint32_t *__restrict__ crc_cur)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || status[i] != CIO_OK) {
+        return;
+    }
+    if (hdr && hdr[kDevHdrStatus] != 0) {
+        status[i] = CIO_ERROR;                // the planner published an empty batch: nothing was copied
+        return;
+    }
+    uint8_t *p = base + img_offs[i];
+    const uint32_t m = (uint32_t) slen[i];
+    p[0] = 0xc1;
+    p[1] = 0x00;
+    p[2] = checksum ? 0xff : 0;
+    p[3] = checksum ? 0x12 : 0;
+    p[4] = checksum ? 0xd9 : 0;
+    p[5] = checksum ? 0x41 : 0;
+    for (uint32_t k = 6; k < 22; ++k) {
+        p[k] = 0;
+    }
+    p[22] = (uint8_t) (m >> 8);
+    p[23] = (uint8_t) m;
+    if (checksum) {
+        crc_cur[i] = crc ? crc[i] : seed[i];
+    }
+}
+
+// ---------------------------------------------------------------- write
+
+__global__ void __launch_bounds__(256)
+write_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restrict__ img_offs,
+              const uint64_t *__restrict__ img_caps, uint32_t n, const uint64_t *__restrict__ src_offs,
+              const uint64_t *__restrict__ src_lens, uint64_t src_bytes, int32_t *__restrict__ status,
+              uint64_t *__restrict__ soff, uint64_t *__restrict__ slen, uint64_t *__restrict__ dst,
+              uint32_t *__restrict__ newlen)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint64_t count = src_lens[i];
+    int32_t st = CIO_OK;
+    uint64_t so = 0, sl = 0, d = 0;
+    uint32_t nl = 0;
+    if (count != 0) {                         // cio_file_write: count == 0 does nothing
+        const uint64_t off = img_offs[i], cap = img_caps[i], s = src_offs[i];
+        uint32_t meta = 0;
+        uint64_t content = 0;
+        if (image_ok(base, dev_bytes, off, cap, meta, content) && count <= kMaxContent &&
+            content + count <= kMaxContent && (uint64_t) kHdrMin + meta + content + count <= cap &&
+            range_ok(s, count, src_bytes)) {
+            so = s;
+            sl = count;
+            d = off + kHdrMin + meta + content;
+            nl = (uint32_t) (content + count);
+        } else {
+            st = CIO_ERROR;
+        }
+    }
+    status[i] = st;
+    soff[i] = so;
+    slen[i] = sl;
+    dst[i] = d;
+    newlen[i] = nl;
+}
+
+__global__ void __launch_bounds__(256)
+write_finish(uint8_t *base, const uint64_t *__restrict__ img_offs, uint32_t n, int32_t *__restrict__ status,
+             const uint64_t *__restrict__ slen, const uint32_t *__restrict__ newlen,
+             const uint32_t *__restrict__ crc, const unsigned long long *__restrict__ hdr, int checksum,
+             uint32_t *__restrict__ crc_cur)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || status[i] != CIO_OK || slen[i] == 0) {
+        return;
+    }
+    if (hdr[kDevHdrStatus] != 0) {
+        status[i] = CIO_ERROR;                // the planner published an empty batch: nothing was copied
+        return;
+    }
+    uint8_t *p = base + img_offs[i];
+    if (checksum) {
+        const uint32_t c = crc[i];
+        crc_cur[i] = c;
+        p[2] = (uint8_t) c;                   // raw state in an 8-byte crc_t, host byte order
+        p[3] = (uint8_t) (c >> 8);
+        p[4] = (uint8_t) (c >> 16);
+        p[5] = (uint8_t) (c >> 24);
+        p[6] = p[7] = p[8] = p[9] = 0;
+    }
+    put_be32(p + 10, newlen[i]);
+}
+
+// ---------------------------------------------------------------- seal
+
+// Validates; with CIOA_SEAL_RECOMPUTE (soff, slen not NULL) the emitted CRC
+// region is [img + 22, + 2 + meta + content), zero-length for a rejected image.
+__global__ void __launch_bounds__(256)
+seal_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restrict__ img_offs,
+             const uint64_t *__restrict__ img_caps, uint32_t n, int32_t *__restrict__ status,
+             uint64_t *__restrict__ soff, uint64_t *__restrict__ slen)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint64_t off = img_offs[i];
+    uint32_t meta = 0;
+    uint64_t content = 0;
+    const bool ok = image_ok(base, dev_bytes, off, img_caps[i], meta, content);
+    status[i] = ok ? CIO_OK : CIO_ERROR;
+    if (soff) {
+        soff[i] = ok ? off + 22 : 0;
+        slen[i] = ok ? 2ull + meta + content : 0;
+    }
+}
+
+// crc / hdr: the recomputed states and the planner's header, or NULL.
+__global__ void __launch_bounds__(256)
+seal_finish(uint8_t *base, const uint64_t *__restrict__ img_offs, uint32_t n, int32_t *__restrict__ status,
+            const uint32_t *__restrict__ crc, const unsigned long long *__restrict__ hdr,
+            uint32_t *__restrict__ crc_cur)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || status[i] != CIO_OK) {
+        return;
+    }
+    if (hdr && hdr[kDevHdrStatus] != 0) {
+        status[i] = CIO_ERROR;
+        return;
+    }
+    uint32_t c = crc_cur[i];
+    if (crc) {
+        c = crc[i];
+        crc_cur[i] = c;
+    }
+    uint8_t *p = base + img_offs[i];
+    put_be32(p + 2, c ^ 0xffffffffu);         // htonl(crc_finalize) in an 8-byte crc_t
+    p[6] = p[7] = p[8] = p[9] = 0;
+}
+
+// ---------------------------------------------------------------- the append copy
+// (record_of, copy_units, copy_wave and copy_tiny: write_dev_copy.h)
+
+// Record i: slen[i] bytes from src_base + soff[i] to dst_base + dst[i].  The
+// planner's image of the source regions gives the balance: S steps in all,
+// record i holding steps [desc[i].g, + desc[i].nsteps).  Wave w of the grid
+// takes steps [w S / W, (w + 1) S / W), so one 4 MiB record among thousands of
+// 4 KiB ones spreads over as many waves as its bytes call for.  Records of
+// fewer than 4 bytes have no step (the CRC kernel's tiny list); they are
+// copied bytewise up front.
+__global__ void __launch_bounds__(kCopyThreads)
+append_copy(uint8_t *dst_base, const uint8_t *src_base, const ChunkDesc *__restrict__ desc,
+            const uint64_t *__restrict__ soff, const uint64_t *__restrict__ slen,
+            const uint64_t *__restrict__ dst, const unsigned long long *__restrict__ hdr, uint32_t n)
+{
+    if (hdr[kDevHdrStatus] != 0) {
+        return;
+    }
+    const uint64_t gtid = (uint64_t) blockIdx.x * kCopyThreads + threadIdx.x;
+    const uint64_t nthreads = (uint64_t) gridDim.x * kCopyThreads;
+    if (hdr[kDevHdrNtiny] != 0) {
+        copy_tiny(dst_base, src_base, soff, slen, dst, n, gtid, nthreads);
+    }
+    const uint64_t w = __builtin_amdgcn_readfirstlane((uint32_t) (gtid / kWave));
+    copy_wave(dst_base, src_base, desc, soff, slen, dst, n, hdr[kDevHdrS], (uint64_t) gridDim.x * kCopyWaves, w,
+              threadIdx.x & (kWave - 1));
+}
+
+uint32_t blocks256(size_t n)
+{
+    return (uint32_t) ((n + 255) / 256);
+}
+
+}  // namespace
+
+struct cio_dev_writer {
+    uint32_t max_chunks = 0;                 // first: the argument checks read it
+    cio_crc32_devplan *dp = nullptr;
+    uint32_t copy_grid = 0;
+    uint64_t *soff = nullptr, *slen = nullptr;   // validated source / CRC regions
+    uint64_t *dst = nullptr;                 // destination offsets from dev_base
+    uint32_t *newlen = nullptr;              // content length after the append
+    uint32_t *seed = nullptr;                // init: the CRC state after bytes 22..23
+    uint32_t *crc = nullptr;                 // the CRC launch's output
+};
+
+namespace {
+
+int launch_copy(const cio_dev_writer *w, void *dev_base, const void *dev_src, size_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(append_copy, dim3(w->copy_grid), dim3(kCopyThreads), 0, s,
+                       reinterpret_cast<uint8_t *>(dev_base), reinterpret_cast<const uint8_t *>(dev_src),
+                       w->dp->p->desc, w->soff, w->slen, w->dst, w->dp->hdr, (uint32_t) n);
+    HIP_TRY(hipGetLastError(), "append_copy launch");
+    return CIO_OK;
+}
+
+// The argument checks every entry point shares, before any device call.
+// Returns 1 when the call is a no-op (n == 0), 0 to go on, CIO_ERROR.
+int check_args(const char *who, const cio_dev_writer *w, const void *dev_base, const uint64_t *offs,
+               const uint64_t *caps, size_t n, int flags, int allowed, const uint32_t *crc_cur,
+               const int32_t *status, bool source_ok = true)
+{
+    std::string msg;
+    if (flags & ~allowed) {
+        msg = std::string(who) + ": unknown flags";
+        return fail(msg.c_str());
+    }
+    if ((flags & CIOA_SEAL_RECOMPUTE) && !(flags & CIO_CHECKSUM)) {
+        msg = std::string(who) + ": CIOA_SEAL_RECOMPUTE needs CIO_CHECKSUM";
+        return fail(msg.c_str());
+    }
+    if (!w) {
+        msg = std::string(who) + ": null writer";
+        return fail(msg.c_str());
+    }
+    if (n == 0) {
+        return 1;
+    }
+    if (!dev_base || !offs || !caps || !status || ((flags & CIO_CHECKSUM) && !crc_cur) || !source_ok) {
+        msg = std::string(who) + ": null pointer";
+        return fail(msg.c_str());
+    }
+    if (n > w->max_chunks) {
+        msg = std::string(who) + ": more images than the writer was created for";
+        return fail(msg.c_str());
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void cio_dev_writer_destroy(cio_dev_writer *w)
+{
+    if (!w) {
+        return;
+    }
+    cio_crc32_devplan_destroy(w->dp);
+    (void) hipFree(w->soff);
+    (void) hipFree(w->slen);
+    (void) hipFree(w->dst);
+    (void) hipFree(w->newlen);
+    (void) hipFree(w->seed);
+    (void) hipFree(w->crc);
+    delete w;
+}
+
+int cio_dev_writer_create(cio_dev_writer **out, size_t max_chunks)
+{
+    if (!out) {
+        return fail("cio_dev_writer_create: null argument");
+    }
+    *out = nullptr;
+    if (max_chunks == 0 || max_chunks >= 0xffffffffull) {
+        return fail("cio_dev_writer_create: max_chunks must be 1 .. 2^32 - 2");
+    }
+    DeviceState *st;
+    if (device_state(&st) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    cio_dev_writer *w = new cio_dev_writer();
+    w->max_chunks = (uint32_t) max_chunks;
+    w->copy_grid = (uint32_t) st->cus * kCopyWgPerCu;
+    if (cio_crc32_devplan_create(&w->dp, max_chunks) != CIO_OK) {
+        cio_dev_writer_destroy(w);
+        return CIO_ERROR;
+    }
+    hipError_t e;
+    if ((e = hipMalloc(&w->soff, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->slen, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->dst, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->newlen, max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->seed, max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->crc, max_chunks * sizeof(uint32_t))) != hipSuccess) {
+        cio_dev_writer_destroy(w);
+        return fail("cio_dev_writer_create: device allocation", e);
+    }
+    *out = w;
+    return CIO_OK;
+}
+
+int cio_file_init_batch_dev(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                            const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                            const void *dev_meta_src, uint64_t meta_src_bytes,
+                            const uint64_t *dev_meta_offs, const uint64_t *dev_meta_lens,
+                            int flags, uint32_t *dev_crc_cur, int32_t *dev_status, void *stream)
+{
+    static const char who[] = "cio_file_init_batch_dev";
+    const int rc = check_args(who, w, dev_base, dev_img_offs, dev_img_caps, n, flags, CIO_CHECKSUM, dev_crc_cur,
+                              dev_status, !dev_meta_src || (dev_meta_offs && dev_meta_lens));
+    if (rc != 0) {
+        return rc > 0 ? CIO_OK : rc;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t *base = reinterpret_cast<uint8_t *>(dev_base);
+    const uint32_t nb = blocks256(n);
+    const int checksum = (flags & CIO_CHECKSUM) != 0;
+    const bool meta = dev_meta_src != nullptr;
+    hipLaunchKernelGGL(init_headers, dim3(nb), dim3(256), 0, s, dev_bytes, dev_img_offs, dev_img_caps, (uint32_t) n,
+                       meta ? dev_meta_offs : nullptr, meta ? dev_meta_lens : nullptr, meta_src_bytes, dev_status,
+                       w->soff, w->slen, w->dst, w->seed);
+    HIP_TRY(hipGetLastError(), "cio_file_init_batch_dev: header kernel launch");
+    if (meta) {
+        if (devplan_launch_planner(w->dp, meta_src_bytes, w->soff, w->slen, n, nullptr, s) != CIO_OK ||
+            launch_copy(w, dev_base, dev_meta_src, n, s) != CIO_OK) {
+            return CIO_ERROR;
+        }
+        if (checksum && devplan_crc_launch(w->dp->p, w->dp->hdr, dev_meta_src, w->seed, w->crc, n, s) != CIO_OK) {
+            return CIO_ERROR;
+        }
+    }
+    hipLaunchKernelGGL(init_finish, dim3(nb), dim3(256), 0, s, base, dev_img_offs, (uint32_t) n, dev_status,
+                       w->slen, w->seed, meta && checksum ? w->crc : nullptr, meta ? w->dp->hdr : nullptr, checksum,
+                       dev_crc_cur);
+    HIP_TRY(hipGetLastError(), "cio_file_init_batch_dev: finish kernel launch");
+    return CIO_OK;
+}
+
+int cio_file_write_batch_dev(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                             const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                             const void *dev_src, uint64_t src_bytes,
+                             const uint64_t *dev_src_offs, const uint64_t *dev_src_lens,
+                             int flags, uint32_t *dev_crc_cur, int32_t *dev_status, void *stream)
+{
+    static const char who[] = "cio_file_write_batch_dev";
+    const int rc = check_args(who, w, dev_base, dev_img_offs, dev_img_caps, n, flags, CIO_CHECKSUM, dev_crc_cur,
+                              dev_status, dev_src && dev_src_offs && dev_src_lens);
+    if (rc != 0) {
+        return rc > 0 ? CIO_OK : rc;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t *base = reinterpret_cast<uint8_t *>(dev_base);
+    const uint32_t nb = blocks256(n);
+    const int checksum = (flags & CIO_CHECKSUM) != 0;
+    hipLaunchKernelGGL(write_headers, dim3(nb), dim3(256), 0, s, base, dev_bytes, dev_img_offs, dev_img_caps,
+                       (uint32_t) n, dev_src_offs, dev_src_lens, src_bytes, dev_status, w->soff, w->slen, w->dst,
+                       w->newlen);
+    HIP_TRY(hipGetLastError(), "cio_file_write_batch_dev: header kernel launch");
+    if (devplan_launch_planner(w->dp, src_bytes, w->soff, w->slen, n, nullptr, s) != CIO_OK ||
+        launch_copy(w, dev_base, dev_src, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    if (checksum && devplan_crc_launch(w->dp->p, w->dp->hdr, dev_src, dev_crc_cur, w->crc, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    hipLaunchKernelGGL(write_finish, dim3(nb), dim3(256), 0, s, base, dev_img_offs, (uint32_t) n, dev_status,
+                       w->slen, w->newlen, w->crc, w->dp->hdr, checksum, dev_crc_cur);
+    HIP_TRY(hipGetLastError(), "cio_file_write_batch_dev: finish kernel launch");
+    return CIO_OK;
+}
+
+int cio_file_seal_batch_dev(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                            const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                            int flags, uint32_t *dev_crc_cur, int32_t *dev_status, void *stream)
+{
+    static const char who[] = "cio_file_seal_batch_dev";
+    const int rc = check_args(who, w, dev_base, dev_img_offs, dev_img_caps, n, flags,
+                              CIO_CHECKSUM | CIOA_SEAL_RECOMPUTE, dev_crc_cur, dev_status);
+    if (rc != 0) {
+        return rc > 0 ? CIO_OK : rc;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t *base = reinterpret_cast<uint8_t *>(dev_base);
+    const uint32_t nb = blocks256(n);
+    const bool recompute = (flags & CIOA_SEAL_RECOMPUTE) != 0;
+    hipLaunchKernelGGL(seal_headers, dim3(nb), dim3(256), 0, s, base, dev_bytes, dev_img_offs, dev_img_caps,
+                       (uint32_t) n, dev_status, recompute ? w->soff : nullptr, recompute ? w->slen : nullptr);
+    HIP_TRY(hipGetLastError(), "cio_file_seal_batch_dev: header kernel launch");
+    if (!(flags & CIO_CHECKSUM)) {
+        return CIO_OK;
+    }
+    if (recompute &&
+        (devplan_launch_planner(w->dp, dev_bytes, w->soff, w->slen, n, nullptr, s) != CIO_OK ||
+         devplan_crc_launch(w->dp->p, w->dp->hdr, dev_base, nullptr, w->crc, n, s) != CIO_OK)) {
+        return CIO_ERROR;
+    }
+    hipLaunchKernelGGL(seal_finish, dim3(nb), dim3(256), 0, s, base, dev_img_offs, (uint32_t) n, dev_status,
+                       recompute ? w->crc : nullptr, recompute ? w->dp->hdr : nullptr, dev_crc_cur);
+    HIP_TRY(hipGetLastError(), "cio_file_seal_batch_dev: finish kernel launch");
+    return CIO_OK;
+}
+
+/* Measurement hook (not in the public header; tools/write_dev_ab.py): the
+ * header kernel and the planner of a cio_file_write_batch_dev, then the append
+ * copy kernel ALONE between two HIP events (cio_gpu_event_create).  No CRC and
+ * no finish kernel: the record bytes land, the headers stay as they were, so
+ * the same call can be timed again over the same images. */
+int cioa_debug_write_dev_copy_events(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                                     const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                                     const void *dev_src, uint64_t src_bytes, const uint64_t *dev_src_offs,
+                                     const uint64_t *dev_src_lens, int32_t *dev_status, void *stream,
+                                     void *ev_start, void *ev_stop)
+{
+    if (!w || !dev_base || !dev_img_offs || !dev_img_caps || !dev_src || !dev_src_offs || !dev_src_lens ||
+        !dev_status || !ev_start || !ev_stop || n == 0 || n > w->max_chunks) {
+        return fail("cioa_debug_write_dev_copy_events: bad argument");
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(write_headers, dim3(blocks256(n)), dim3(256), 0, s, reinterpret_cast<const uint8_t *>(dev_base),
+                       dev_bytes, dev_img_offs, dev_img_caps, (uint32_t) n, dev_src_offs, dev_src_lens, src_bytes,
+                       dev_status, w->soff, w->slen, w->dst, w->newlen);
+    HIP_TRY(hipGetLastError(), "cioa_debug_write_dev_copy_events: header kernel launch");
+    if (devplan_launch_planner(w->dp, src_bytes, w->soff, w->slen, n, nullptr, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_start), s), "hipEventRecord");
+    if (launch_copy(w, dev_base, dev_src, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_stop), s), "hipEventRecord");
+    return CIO_OK;
+}
+
+}  // extern "C"
