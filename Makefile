@@ -116,6 +116,14 @@ copycheck:
 	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/copycheck/copy_check tools/copy_check.cpp
 	$(BLD)/copycheck/copy_check
 
+# The in-place move's partition, save / shift split and tile arithmetic
+# (write_dev_move.h, the text the device kernels run) under ASan + UBSan,
+# stand-alone (no GPU, no HIP), the segments of each kernel in three orders.
+movecheck:
+	@mkdir -p $(BLD)/movecheck
+	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/movecheck/move_check tools/move_check.cpp
+	$(BLD)/movecheck/move_check
+
 # make install PREFIX=/usr/local: the library, the public headers (crc32/crc32.h,
 # sha1/sha1.h, chunkio_amd/*.h) and a pkg-config file, for a chunkio build to
 # link against.
@@ -134,4 +142,4 @@ clean:
 	rm -rf $(BLD) $(LIB) $(CTEST)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck copycheck install
+.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck copycheck movecheck install

@@ -11,7 +11,9 @@ Layers:
                                                    (cioa_chunk.h: write/sync/verify/tx/scan,
                                                    up_batch) and of the device-side write
                                                    path (cio_write_dev.h: DevWriter,
-                                                   init / write / seal_batch_dev)
+                                                   init / write / seal_batch_dev;
+                                                   cio_write_dev_move.h:
+                                                   write_metadata / write_at_batch_dev)
 """
 from ._lib import LIB_PATH, CioGpuError, lib  # noqa: F401
 from .crc32 import (  # noqa: F401
@@ -23,7 +25,8 @@ from .crc32 import (  # noqa: F401
 )
 
 from .chunkfile import (  # noqa: F401,E402
-    CIOA_SEAL_RECOMPUTE, DevWriter, init_batch_dev, seal_batch_dev, verify_batch_dev, write_batch_dev,
+    CIOA_SEAL_RECOMPUTE, CIOA_WRITER_MOVE, DevWriter, init_batch_dev, seal_batch_dev, verify_batch_dev,
+    write_at_batch_dev, write_batch_dev, write_metadata_batch_dev,
 )
 
 __version__ = "0.5.0"

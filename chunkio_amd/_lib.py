@@ -42,6 +42,9 @@ EXPORTS = (
     # include/chunkio_amd/cio_write_dev.h
     "cio_dev_writer_create", "cio_dev_writer_destroy", "cio_file_init_batch_dev", "cio_file_write_batch_dev",
     "cio_file_seal_batch_dev",
+    # include/chunkio_amd/cio_write_dev_move.h
+    "cio_dev_writer_create_ex", "cio_dev_writer_move_segments", "cio_file_write_metadata_batch_dev",
+    "cio_file_write_at_batch_dev",
     # include/chunkio_amd/cio_sync.h
     "cio_file_sync_batch", "cio_file_sync_batch_multi", "cio_file_sync_batch_begin", "cio_file_sync_batch_end",
     # include/chunkio_amd/cioa_chunk.h
@@ -104,6 +107,12 @@ def _bind(lib):
                                                     V, V, ctypes.c_int, V, V, V]),
         "cio_file_seal_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int,
                                                    V, V, V]),
+        "cio_dev_writer_create_ex": (ctypes.c_int, [P(V), ctypes.c_size_t, ctypes.c_int]),
+        "cio_dev_writer_move_segments": (ctypes.c_uint32, [V]),
+        "cio_file_write_metadata_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V,
+                                                             ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
+        "cio_file_write_at_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V,
+                                                       ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
         "cio_crc32_batch_host": (ctypes.c_int, [P(V), P(ctypes.c_size_t), c_u32_p, c_u32_p,
                                                 ctypes.c_size_t]),
         "cio_crc32_batch_host_multi": (ctypes.c_int, [P(V), P(ctypes.c_size_t), c_u32_p, c_u32_p,

@@ -28,7 +28,11 @@ DevWriter with init_batch_dev / write_batch_dev / seal_batch_dev is the write
 lifecycle of chunk images that live in device memory
 (include/chunkio_amd/cio_write_dev.h): write_init_header, cio_file_write +
 update_checksum and finalize_checksum (src/cio_file.c:149-162, 994-1073,
-97-124) in batches, on cuda tensors, without waiting.
+97-124) in batches, on cuda tensors, without waiting.  DevWriter(n, move=True)
+with write_metadata_batch_dev replaces the metadata of images that already
+hold content (cio_file_write_metadata, src/cio_file.c:1075-1145: the content
+moves inside the image), and write_at_batch_dev is cio_chunk_write_at
+(src/cio_chunk.c:184-209); include/chunkio_amd/cio_write_dev_move.h.
 """
 import ctypes
 import os
@@ -48,6 +52,7 @@ CIOA_VERIFY_DELETE_IRRECOVERABLE = 16
 CIOA_VERIFY_WRITEBACK = 64
 CIOA_SYNC_FINALIZE, CIOA_SYNC_MSYNC, CIOA_SYNC_FULL = 1, 2, 8
 CIOA_SEAL_RECOMPUTE = 256
+CIOA_WRITER_MOVE = 1
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -187,15 +192,23 @@ def verify_batch_dev(plan, base, img_offs, img_sizes, flags=CIO_CHECKSUM, stream
 
 class DevWriter:
     """A writer of chunk images in device memory (cio_dev_writer_*): a device
-    plan and arenas for batches of up to max_chunks images.  Not thread-safe;
-    one call in flight at a time."""
+    plan and arenas for batches of up to max_chunks images.  move=True
+    (CIOA_WRITER_MOVE) adds the scratch arena of the in-place move, which
+    write_metadata_batch_dev needs.  Not thread-safe; one call in flight at a
+    time."""
 
-    def __init__(self, max_chunks):
+    def __init__(self, max_chunks, move=False):
         self.max_chunks = int(max_chunks)
         handle = ctypes.c_void_p()
-        _lib.check(_lib.lib().cio_dev_writer_create(ctypes.byref(handle), self.max_chunks),
-                   "cio_dev_writer_create")
+        _lib.check(_lib.lib().cio_dev_writer_create_ex(ctypes.byref(handle), self.max_chunks,
+                                                       CIOA_WRITER_MOVE if move else 0),
+                   "cio_dev_writer_create_ex")
         self._handle = handle
+
+    @property
+    def move_segments(self):
+        """Segments the move partitions a batch into; 0 without move=True."""
+        return int(_lib.lib().cio_dev_writer_move_segments(self._handle)) if self._handle else 0
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -261,6 +274,44 @@ def write_batch_dev(writer, base, img_offs, img_caps, src, src_offs, src_lens, c
         _ptr(src), src.numel() * src.element_size(), _ptr(src_offs), _ptr(src_lens), int(flags), _ptr(crc_cur),
         _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_write_batch_dev")
+    return status[:n]
+
+
+def write_metadata_batch_dev(writer, base, img_offs, img_caps, meta_src, meta_offs, meta_lens, crc_cur,
+                             flags=CIO_CHECKSUM, status=None, stream=None):
+    """Replace the metadata of image i by meta_src[meta_offs[i]:+meta_lens[i]]
+    (cio_file_write_metadata_batch_dev): the content moves inside the image by
+    the difference of the lengths, bytes 22..23 take the new length, and with
+    CIO_CHECKSUM crc_cur is recomputed in place over the new layout.  writer: a
+    DevWriter(..., move=True).  An entry whose new layout does not fit its
+    capacity is refused (status CIO_ERROR, nothing changed).  Returns the
+    status cuda tensor (int32) without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_write_metadata_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n,
+        _ptr(meta_src), meta_src.numel() * meta_src.element_size(), _ptr(meta_offs), _ptr(meta_lens), int(flags),
+        _ptr(crc_cur), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_write_metadata_batch_dev")
+    return status[:n]
+
+
+def write_at_batch_dev(writer, base, img_offs, img_caps, at_offs, src, src_offs, src_lens, crc_cur,
+                       flags=CIO_CHECKSUM, status=None, stream=None):
+    """Cut the content of image i to at_offs[i] bytes and append record i,
+    src[src_offs[i]:+src_lens[i]], there (cio_file_write_at_batch_dev); with
+    CIO_CHECKSUM crc_cur is recomputed over the kept prefix and chained over
+    the record.  at_offs[i] beyond the content is refused; a record of length
+    0 is a no-op.  Returns the status cuda tensor (int32) without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_write_at_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n,
+        _ptr(at_offs), _ptr(src), src.numel() * src.element_size(), _ptr(src_offs), _ptr(src_lens), int(flags),
+        _ptr(crc_cur), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_write_at_batch_dev")
     return status[:n]
 
 

@@ -1,6 +1,7 @@
 // write_dev_gpu.hip -- chunkio's write lifecycle for chunk images in HBM, for
-// CDNA4 (gfx950, MI355X): initialise, append, seal.  C ABI in
-// include/chunkio_amd/cio_write_dev.h; DESIGN.md §14.
+// CDNA4 (gfx950, MI355X): initialise, append, seal, and -- on what is already
+// in an image -- replace the metadata and write_at.  C ABI in
+// include/chunkio_amd/cio_write_dev.h and cio_write_dev_move.h; DESIGN.md §14.
 //
 // An append batch is a serial chain of kernels on the caller's stream:
 //
@@ -25,6 +26,29 @@
 // verify-on-load's chain (header kernel, planner + CRC over the image regions)
 // with a finish kernel that stores instead of comparing.
 //
+// Replacing the metadata (cio_file_write_metadata_batch_dev) shifts the content
+// of every image onto itself by new - old metadata length:
+//
+//   meta_headers   the checks; the move's regions (old content, delta), the
+//                  metadata records as an append copy's, the CRC region on the
+//                  NEW layout and its seed (the state after the new bytes 22..23)
+//   planner        over the move's source regions
+//   move_save      } the in-place, overlapping, byte-balanced move:
+//   move_shift     } write_dev_move.h
+//   planner, append_copy    the metadata records to byte 24 (after the shift:
+//                  a longer metadata lands on the old content's first bytes)
+//   planner, CRC   over [img + 24, + m + content) of the moved image
+//   meta_finish    accepted entries only: bytes 22..23, crc_cur
+//
+// No kernel before meta_finish touches a rejected image: its regions have
+// length zero.  write_at (cio_file_write_at_batch_dev) is the seal-recompute
+// chain over the kept prefix [img + 22, + 2 + meta + at) into the writer's seed
+// arena, then the append chain with the CRC launch seeded from there.
+//
+// The planner's own checks (a region outside dev_bytes, a region of 2^32
+// steps, a batch of 2^40 steps) cannot fire in those chains' region passes:
+// every region lies inside an image the header kernel found inside dev_bytes.
+//
 // The layout (cio_layout.h holds it for the host) restated for the device:
 //   0..1 magic C1 00 | 2..9 CRC (8-byte crc_t) | 10..13 content length BE
 //   22..23 metadata length BE | 24.. metadata, then content.
@@ -34,7 +58,9 @@
 
 #include "cio_gpu_internal.h"
 #include "write_dev_copy.h"
+#include "write_dev_move.h"
 #include "chunkio_amd/cio_write_dev.h"
+#include "chunkio_amd/cio_write_dev_move.h"
 
 using namespace cioa;
 
@@ -45,6 +71,7 @@ constexpr uint32_t kCopyThreads = 256;                 // 4 waves per workgroup
 constexpr uint32_t kCopyWaves = kCopyThreads / kWave;
 constexpr uint32_t kCopyWgPerCu = 8;                   // 32 waves per CU in flight
 constexpr uint64_t kMaxContent = 0xffffffffull;        // the length field is 32 bits
+constexpr uint32_t kMoveWgPerCu = 4;                   // 32 waves per CU, 128 KiB of loads in flight
 
 __device__ __forceinline__ uint32_t be32(const uint8_t *p)
 {
@@ -293,6 +320,230 @@ append_copy(uint8_t *dst_base, const uint8_t *src_base, const ChunkDesc *__restr
               threadIdx.x & (kWave - 1));
 }
 
+// ---------------------------------------------------------------- write_at
+
+// As write_headers, with the content cut to at[i] first; also the CRC region
+// of the kept prefix, [img + 22, + 2 + meta + at), zero-length for an entry
+// that is rejected or has no record.
+__global__ void __launch_bounds__(256)
+write_at_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restrict__ img_offs,
+                 const uint64_t *__restrict__ img_caps, uint32_t n, const uint64_t *__restrict__ at_offs,
+                 const uint64_t *__restrict__ src_offs, const uint64_t *__restrict__ src_lens, uint64_t src_bytes,
+                 int32_t *__restrict__ status, uint64_t *__restrict__ soff, uint64_t *__restrict__ slen,
+                 uint64_t *__restrict__ dst, uint32_t *__restrict__ newlen, uint64_t *__restrict__ roff,
+                 uint64_t *__restrict__ rlen)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint64_t count = src_lens[i];
+    int32_t st = CIO_OK;
+    uint64_t so = 0, sl = 0, d = 0, ro = 0, rl = 0;
+    uint32_t nl = 0;
+    if (count != 0) {
+        const uint64_t off = img_offs[i], cap = img_caps[i], s = src_offs[i], at = at_offs[i];
+        uint32_t meta = 0;
+        uint64_t content = 0;
+        if (image_ok(base, dev_bytes, off, cap, meta, content) && at <= content && count <= kMaxContent &&
+            at + count <= kMaxContent && (uint64_t) kHdrMin + meta + at + count <= cap &&
+            range_ok(s, count, src_bytes)) {
+            so = s;
+            sl = count;
+            d = off + kHdrMin + meta + at;
+            nl = (uint32_t) (at + count);
+            ro = off + 22;
+            rl = 2ull + meta + at;
+        } else {
+            st = CIO_ERROR;
+        }
+    }
+    status[i] = st;
+    soff[i] = so;
+    slen[i] = sl;
+    dst[i] = d;
+    newlen[i] = nl;
+    roff[i] = ro;
+    rlen[i] = rl;
+}
+
+// ---------------------------------------------------------------- write_metadata
+
+__global__ void __launch_bounds__(256)
+meta_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restrict__ img_offs,
+             const uint64_t *__restrict__ img_caps, uint32_t n, const uint64_t *__restrict__ meta_offs,
+             const uint64_t *__restrict__ meta_lens, uint64_t meta_src_bytes, int32_t *__restrict__ status,
+             uint64_t *__restrict__ soff, uint64_t *__restrict__ slen, uint64_t *__restrict__ dst,
+             uint64_t *__restrict__ msrc, uint64_t *__restrict__ mlen, int64_t *__restrict__ mdelta,
+             uint64_t *__restrict__ roff, uint64_t *__restrict__ rlen, uint32_t *__restrict__ seed)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint64_t off = img_offs[i], cap = img_caps[i], moff = meta_offs[i], m = meta_lens[i];
+    uint32_t old = 0;
+    uint64_t content = 0;
+    const bool ok = image_ok(base, dev_bytes, off, cap, old, content) && m <= 65535u &&
+                    (uint64_t) kHdrMin + m + content <= cap && range_ok(moff, m, meta_src_bytes);
+    const int64_t delta = ok ? (int64_t) m - (int64_t) old : 0;
+    status[i] = ok ? CIO_OK : CIO_ERROR;
+    soff[i] = ok && m ? moff : 0;
+    slen[i] = ok ? m : 0;
+    dst[i] = ok ? off + kHdrMin : 0;
+    msrc[i] = ok ? off + kHdrMin + old : 0;
+    mlen[i] = delta != 0 ? content : 0;       // m == old: the metadata is rewritten in place, nothing moves
+    mdelta[i] = delta;
+    roff[i] = ok ? off + kHdrMin : 0;
+    rlen[i] = ok ? m + content : 0;
+    seed[i] = crc_byte(crc_byte(0xffffffffu, (uint32_t) (m >> 8) & 0xffu), (uint32_t) m & 0xffu);
+}
+
+// crc: the CRC launch's output, or NULL without CIO_CHECKSUM; hdr: the last
+// planner's header; the new metadata length is slen[i].
+__global__ void __launch_bounds__(256)
+meta_finish(uint8_t *base, const uint64_t *__restrict__ img_offs, uint32_t n, int32_t *__restrict__ status,
+            const uint64_t *__restrict__ slen, const uint32_t *__restrict__ crc,
+            const unsigned long long *__restrict__ hdr, uint32_t *__restrict__ crc_cur)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || status[i] != CIO_OK) {
+        return;
+    }
+    if (hdr[kDevHdrStatus] != 0) {
+        status[i] = CIO_ERROR;
+        return;
+    }
+    uint8_t *p = base + img_offs[i];
+    const uint32_t m = (uint32_t) slen[i];
+    p[22] = (uint8_t) (m >> 8);
+    p[23] = (uint8_t) m;
+    if (crc) {
+        crc_cur[i] = crc[i];
+    }
+}
+
+// ---------------------------------------------------------------- the in-place move
+// (move_window, move_range, the tile and move_tiny: write_dev_move.h)
+
+// The save kernel's tiles, dealt to the workgroup's waves in turn: nothing it
+// reads is written in this kernel, so a wave loads and stores at once.
+struct SaveTile {
+    uint32_t lane, wave, next;
+    __device__ __forceinline__ void tile(uint8_t *d, const uint8_t *s, uint64_t len)
+    {
+        if (next == wave) {
+            MoveRegs r;
+            tile_load(r, d, s, len, lane);
+            tile_store(r, d, len, lane);
+        }
+        next = next + 1 == kMoveWaves ? 0 : next + 1;
+    }
+    __device__ __forceinline__ void end() const {}
+};
+
+// The shift kernel's tiles, kMoveWaves to a phase, one per wave: every lane of
+// the workgroup has its loads in registers before any lane stores.  The walk
+// that deals the tiles is the same in every lane, so every lane reaches every
+// barrier.  "In registers" means the loads have RETURNED: __syncthreads()
+// alone lets plain global loads stay in flight across the barrier on this
+// target (the wait for them is placed at their first use, after it), so the
+// wait is stated before the barrier.  It costs nothing: the stores need the
+// same data.
+struct ShiftTile {
+    uint32_t lane, wave, pending;
+    bool mine;
+    uint8_t *d;
+    const uint8_t *s;
+    uint64_t len;
+    __device__ __forceinline__ void tile(uint8_t *d_, const uint8_t *s_, uint64_t len_)
+    {
+        if (pending == wave) {
+            mine = true;
+            d = d_;
+            s = s_;
+            len = len_;
+        }
+        if (++pending == kMoveWaves) {
+            end();
+        }
+    }
+    __device__ __forceinline__ void end()
+    {
+        if (pending == 0) {
+            return;
+        }
+        MoveRegs r;
+        if (mine) {
+            tile_load(r, d, s, len, lane);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0); expcnt and lgkmcnt not waited for
+        __syncthreads();
+        if (mine) {
+            tile_store(r, d, len, lane);
+        }
+        mine = false;
+        pending = 0;
+    }
+};
+
+// Segment blockIdx.x of gridDim.x: its even share of the S steps, walked window
+// by window.  Every condition here is the same in all lanes of the workgroup.
+template <bool SAVE, class Ex>
+__device__ __forceinline__ void move_segment(uint8_t *base, uint8_t *arena, const ChunkDesc *desc,
+                                             const uint64_t *msrc, const uint64_t *mlen, const int64_t *mdelta,
+                                             uint32_t n, uint64_t S, Ex &ex)
+{
+    __shared__ MoveRec win[kMoveWindow];
+    uint64_t t = ((uint64_t) blockIdx.x * S) / gridDim.x;
+    const uint64_t t1 = (((uint64_t) blockIdx.x + 1) * S) / gridDim.x;
+    if (t >= t1) {
+        return;
+    }
+    uint8_t *slots = arena + (uint64_t) blockIdx.x * kMoveSegBytes;
+    uint32_t c = record_of(desc, n, t);
+    while (t < t1 && c < n) {
+        const uint32_t nw = min(kMoveWindow, n - c);
+        __syncthreads();                      // nobody reads the window before it is replaced
+        if (threadIdx.x < nw) {
+            win[threadIdx.x] = move_rec(desc, msrc, mlen, mdelta, c + threadIdx.x);
+        }
+        __syncthreads();
+        move_window<SAVE>(base, slots, win, c, nw, t, t1, c, ex);
+    }
+    ex.end();                                 // the last phase, if it is not full
+}
+
+// One workgroup per segment; arena: gridDim.x * kMoveSegBytes.
+__global__ void __launch_bounds__(kMoveThreads)
+move_save(uint8_t *base, uint8_t *arena, const ChunkDesc *__restrict__ desc, const uint64_t *__restrict__ msrc,
+          const uint64_t *__restrict__ mlen, const int64_t *__restrict__ mdelta,
+          const unsigned long long *__restrict__ hdr, uint32_t n)
+{
+    if (hdr[kDevHdrStatus] != 0) {
+        return;
+    }
+    SaveTile ex = {threadIdx.x & (kWave - 1), (uint32_t) __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), 0};
+    move_segment<true>(base, arena, desc, msrc, mlen, mdelta, n, hdr[kDevHdrS], ex);
+}
+
+__global__ void __launch_bounds__(kMoveThreads)
+move_shift(uint8_t *base, uint8_t *arena, const ChunkDesc *__restrict__ desc, const uint64_t *__restrict__ msrc,
+           const uint64_t *__restrict__ mlen, const int64_t *__restrict__ mdelta,
+           const unsigned long long *__restrict__ hdr, uint32_t n)
+{
+    if (hdr[kDevHdrStatus] != 0) {
+        return;
+    }
+    if (hdr[kDevHdrNtiny] != 0) {
+        move_tiny(base, msrc, mlen, mdelta, n, (uint64_t) blockIdx.x * kMoveThreads + threadIdx.x,
+                  (uint64_t) gridDim.x * kMoveThreads);
+    }
+    ShiftTile ex = {threadIdx.x & (kWave - 1), (uint32_t) __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), 0,
+                    false, nullptr, nullptr, 0};
+    move_segment<false>(base, arena, desc, msrc, mlen, mdelta, n, hdr[kDevHdrS], ex);
+}
+
 uint32_t blocks256(size_t n)
 {
     return (uint32_t) ((n + 255) / 256);
@@ -304,11 +555,16 @@ struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
     cio_crc32_devplan *dp = nullptr;
     uint32_t copy_grid = 0;
+    uint32_t move_grid = 0;                  // segments of the in-place move; 0 without CIOA_WRITER_MOVE
     uint64_t *soff = nullptr, *slen = nullptr;   // validated source / CRC regions
     uint64_t *dst = nullptr;                 // destination offsets from dev_base
     uint32_t *newlen = nullptr;              // content length after the append
     uint32_t *seed = nullptr;                // init: the CRC state after bytes 22..23
     uint32_t *crc = nullptr;                 // the CRC launch's output
+    uint64_t *roff = nullptr, *rlen = nullptr;   // write_at, write_metadata: the CRC region in the image
+    uint64_t *msrc = nullptr, *mlen = nullptr;   // the move: old content (with CIOA_WRITER_MOVE)
+    int64_t *mdelta = nullptr;               // new - old metadata length
+    uint8_t *arena = nullptr;                // move_grid * kMoveSegBytes
 };
 
 namespace {
@@ -355,6 +611,28 @@ int check_args(const char *who, const cio_dev_writer *w, const void *dev_base, c
     return 0;
 }
 
+int launch_meta_headers(const cio_dev_writer *w, const uint8_t *base, uint64_t dev_bytes, const uint64_t *offs,
+                        const uint64_t *caps, size_t n, uint64_t meta_src_bytes, const uint64_t *meta_offs,
+                        const uint64_t *meta_lens, int32_t *status, hipStream_t s)
+{
+    hipLaunchKernelGGL(meta_headers, dim3(blocks256(n)), dim3(256), 0, s, base, dev_bytes, offs, caps, (uint32_t) n,
+                       meta_offs, meta_lens, meta_src_bytes, status, w->soff, w->slen, w->dst, w->msrc, w->mlen,
+                       w->mdelta, w->roff, w->rlen, w->seed);
+    HIP_TRY(hipGetLastError(), "cio_file_write_metadata_batch_dev: header kernel launch");
+    return CIO_OK;
+}
+
+// move_save and move_shift over the planner's image of (msrc, mlen).
+int launch_move(const cio_dev_writer *w, uint8_t *base, size_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(move_save, dim3(w->move_grid), dim3(kMoveThreads), 0, s, base, w->arena, w->dp->p->desc,
+                       w->msrc, w->mlen, w->mdelta, w->dp->hdr, (uint32_t) n);
+    hipLaunchKernelGGL(move_shift, dim3(w->move_grid), dim3(kMoveThreads), 0, s, base, w->arena, w->dp->p->desc,
+                       w->msrc, w->mlen, w->mdelta, w->dp->hdr, (uint32_t) n);
+    HIP_TRY(hipGetLastError(), "move launch");
+    return CIO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -371,10 +649,26 @@ void cio_dev_writer_destroy(cio_dev_writer *w)
     (void) hipFree(w->newlen);
     (void) hipFree(w->seed);
     (void) hipFree(w->crc);
+    (void) hipFree(w->roff);
+    (void) hipFree(w->rlen);
+    (void) hipFree(w->msrc);
+    (void) hipFree(w->mlen);
+    (void) hipFree(w->mdelta);
+    (void) hipFree(w->arena);
     delete w;
 }
 
 int cio_dev_writer_create(cio_dev_writer **out, size_t max_chunks)
+{
+    return cio_dev_writer_create_ex(out, max_chunks, 0);
+}
+
+uint32_t cio_dev_writer_move_segments(const cio_dev_writer *w)
+{
+    return w ? w->move_grid : 0;
+}
+
+int cio_dev_writer_create_ex(cio_dev_writer **out, size_t max_chunks, int flags)
 {
     if (!out) {
         return fail("cio_dev_writer_create: null argument");
@@ -382,6 +676,9 @@ int cio_dev_writer_create(cio_dev_writer **out, size_t max_chunks)
     *out = nullptr;
     if (max_chunks == 0 || max_chunks >= 0xffffffffull) {
         return fail("cio_dev_writer_create: max_chunks must be 1 .. 2^32 - 2");
+    }
+    if (flags & ~CIOA_WRITER_MOVE) {
+        return fail("cio_dev_writer_create_ex: unknown flags");
     }
     DeviceState *st;
     if (device_state(&st) != CIO_OK) {
@@ -400,9 +697,22 @@ int cio_dev_writer_create(cio_dev_writer **out, size_t max_chunks)
         (e = hipMalloc(&w->dst, max_chunks * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMalloc(&w->newlen, max_chunks * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc(&w->seed, max_chunks * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc(&w->crc, max_chunks * sizeof(uint32_t))) != hipSuccess) {
+        (e = hipMalloc(&w->crc, max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->roff, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->rlen, max_chunks * sizeof(uint64_t))) != hipSuccess) {
         cio_dev_writer_destroy(w);
         return fail("cio_dev_writer_create: device allocation", e);
+    }
+    if (flags & CIOA_WRITER_MOVE) {
+        const uint32_t grid = (uint32_t) st->cus * kMoveWgPerCu;
+        if ((e = hipMalloc(&w->msrc, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+            (e = hipMalloc(&w->mlen, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+            (e = hipMalloc(&w->mdelta, max_chunks * sizeof(int64_t))) != hipSuccess ||
+            (e = hipMalloc(&w->arena, (size_t) grid * kMoveSegBytes)) != hipSuccess) {
+            cio_dev_writer_destroy(w);
+            return fail("cio_dev_writer_create_ex: device allocation", e);
+        }
+        w->move_grid = grid;
     }
     *out = w;
     return CIO_OK;
@@ -506,6 +816,113 @@ int cio_file_seal_batch_dev(cio_dev_writer *w, void *dev_base, uint64_t dev_byte
     hipLaunchKernelGGL(seal_finish, dim3(nb), dim3(256), 0, s, base, dev_img_offs, (uint32_t) n, dev_status,
                        recompute ? w->crc : nullptr, recompute ? w->dp->hdr : nullptr, dev_crc_cur);
     HIP_TRY(hipGetLastError(), "cio_file_seal_batch_dev: finish kernel launch");
+    return CIO_OK;
+}
+
+int cio_file_write_at_batch_dev(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                                const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                                const uint64_t *dev_at_offs,
+                                const void *dev_src, uint64_t src_bytes,
+                                const uint64_t *dev_src_offs, const uint64_t *dev_src_lens,
+                                int flags, uint32_t *dev_crc_cur, int32_t *dev_status, void *stream)
+{
+    static const char who[] = "cio_file_write_at_batch_dev";
+    const int rc = check_args(who, w, dev_base, dev_img_offs, dev_img_caps, n, flags, CIO_CHECKSUM, dev_crc_cur,
+                              dev_status, dev_at_offs && dev_src && dev_src_offs && dev_src_lens);
+    if (rc != 0) {
+        return rc > 0 ? CIO_OK : rc;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t *base = reinterpret_cast<uint8_t *>(dev_base);
+    const uint32_t nb = blocks256(n);
+    const int checksum = (flags & CIO_CHECKSUM) != 0;
+    hipLaunchKernelGGL(write_at_headers, dim3(nb), dim3(256), 0, s, base, dev_bytes, dev_img_offs, dev_img_caps,
+                       (uint32_t) n, dev_at_offs, dev_src_offs, dev_src_lens, src_bytes, dev_status, w->soff,
+                       w->slen, w->dst, w->newlen, w->roff, w->rlen);
+    HIP_TRY(hipGetLastError(), "cio_file_write_at_batch_dev: header kernel launch");
+    // the crc_reset recompute over the kept prefix, into the seed arena
+    if (checksum &&
+        (devplan_launch_planner(w->dp, dev_bytes, w->roff, w->rlen, n, nullptr, s) != CIO_OK ||
+         devplan_crc_launch(w->dp->p, w->dp->hdr, dev_base, nullptr, w->seed, n, s) != CIO_OK)) {
+        return CIO_ERROR;
+    }
+    if (devplan_launch_planner(w->dp, src_bytes, w->soff, w->slen, n, nullptr, s) != CIO_OK ||
+        launch_copy(w, dev_base, dev_src, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    if (checksum && devplan_crc_launch(w->dp->p, w->dp->hdr, dev_src, w->seed, w->crc, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    hipLaunchKernelGGL(write_finish, dim3(nb), dim3(256), 0, s, base, dev_img_offs, (uint32_t) n, dev_status,
+                       w->slen, w->newlen, w->crc, w->dp->hdr, checksum, dev_crc_cur);
+    HIP_TRY(hipGetLastError(), "cio_file_write_at_batch_dev: finish kernel launch");
+    return CIO_OK;
+}
+
+int cio_file_write_metadata_batch_dev(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                                      const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                                      const void *dev_meta_src, uint64_t meta_src_bytes,
+                                      const uint64_t *dev_meta_offs, const uint64_t *dev_meta_lens,
+                                      int flags, uint32_t *dev_crc_cur, int32_t *dev_status, void *stream)
+{
+    static const char who[] = "cio_file_write_metadata_batch_dev";
+    const int rc = check_args(who, w, dev_base, dev_img_offs, dev_img_caps, n, flags, CIO_CHECKSUM, dev_crc_cur,
+                              dev_status, dev_meta_src && dev_meta_offs && dev_meta_lens);
+    if (rc != 0) {
+        return rc > 0 ? CIO_OK : rc;
+    }
+    if (w->move_grid == 0) {
+        return fail("cio_file_write_metadata_batch_dev: the writer was created without CIOA_WRITER_MOVE");
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t *base = reinterpret_cast<uint8_t *>(dev_base);
+    const int checksum = (flags & CIO_CHECKSUM) != 0;
+    if (launch_meta_headers(w, base, dev_bytes, dev_img_offs, dev_img_caps, n, meta_src_bytes, dev_meta_offs,
+                            dev_meta_lens, dev_status, s) != CIO_OK ||
+        devplan_launch_planner(w->dp, dev_bytes, w->msrc, w->mlen, n, nullptr, s) != CIO_OK ||
+        launch_move(w, base, n, s) != CIO_OK ||
+        devplan_launch_planner(w->dp, meta_src_bytes, w->soff, w->slen, n, nullptr, s) != CIO_OK ||
+        launch_copy(w, dev_base, dev_meta_src, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    if (checksum &&
+        (devplan_launch_planner(w->dp, dev_bytes, w->roff, w->rlen, n, nullptr, s) != CIO_OK ||
+         devplan_crc_launch(w->dp->p, w->dp->hdr, dev_base, w->seed, w->crc, n, s) != CIO_OK)) {
+        return CIO_ERROR;
+    }
+    hipLaunchKernelGGL(meta_finish, dim3(blocks256(n)), dim3(256), 0, s, base, dev_img_offs, (uint32_t) n,
+                       dev_status, w->slen, checksum ? w->crc : nullptr, w->dp->hdr, dev_crc_cur);
+    HIP_TRY(hipGetLastError(), "cio_file_write_metadata_batch_dev: finish kernel launch");
+    return CIO_OK;
+}
+
+/* Measurement hook (not in the public header; tools/write_dev_move_ab.py): the
+ * header kernel and the move's planner of a cio_file_write_metadata_batch_dev,
+ * then move_save + move_shift ALONE between two HIP events.  No metadata copy,
+ * no CRC and no finish kernel: the content lands at its new place, the headers
+ * stay as they were, so the same call can be timed again over the same images. */
+int cioa_debug_write_dev_move_events(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes,
+                                     const uint64_t *dev_img_offs, const uint64_t *dev_img_caps, size_t n,
+                                     uint64_t meta_src_bytes, const uint64_t *dev_meta_offs,
+                                     const uint64_t *dev_meta_lens, int32_t *dev_status, void *stream,
+                                     void *ev_start, void *ev_stop)
+{
+    if (!w || !dev_base || !dev_img_offs || !dev_img_caps || !dev_meta_offs || !dev_meta_lens || !dev_status ||
+        !ev_start || !ev_stop || n == 0 || n > w->max_chunks || w->move_grid == 0) {
+        return fail("cioa_debug_write_dev_move_events: bad argument");
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint8_t *base = reinterpret_cast<uint8_t *>(dev_base);
+    if (launch_meta_headers(w, base, dev_bytes, dev_img_offs, dev_img_caps, n, meta_src_bytes, dev_meta_offs,
+                            dev_meta_lens, dev_status, s) != CIO_OK ||
+        devplan_launch_planner(w->dp, dev_bytes, w->msrc, w->mlen, n, nullptr, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_start), s), "hipEventRecord");
+    if (launch_move(w, base, n, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
+    HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_stop), s), "hipEventRecord");
     return CIO_OK;
 }
 

@@ -51,9 +51,10 @@
  *   - one call in flight per writer (the writer's arenas hold the batch's
  *     plan between its kernels); not thread-safe.
  *
- * Only metadata written BEFORE content is supported (at init).  Metadata
- * written or replaced after content moves the content (cio_file_write_metadata,
- * src/cio_file.c:1075-1145) and stays a host operation.
+ * Metadata written or replaced AFTER content moves the content inside the
+ * image (cio_file_write_metadata, src/cio_file.c:1075-1145), and write_at cuts
+ * it: both are in cio_write_dev_move.h, which extends this header.  Growing an
+ * image stays out of scope.
  */
 #ifndef CIO_WRITE_DEV_H
 #define CIO_WRITE_DEV_H
