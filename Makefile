@@ -19,7 +19,7 @@ HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -std=c++17 -Wall $(INC) -munsafe-fp
             -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-kernarg-preload-count=9
 
 COBJS   := $(BLD)/host_copy.o $(BLD)/crc32_host.o $(BLD)/crc32_scalar.o $(BLD)/cio_verify.o $(BLD)/cio_sync.o $(BLD)/cioa_chunk.o $(BLD)/crc_route.o $(BLD)/crc_cpu_batch.o $(BLD)/cio_sha1.o
-HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o
+HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o
 
 CTEST   := tests/c/bin
 REF_INC := /root/reference/include/chunkio/cio_crc32.h
@@ -89,17 +89,19 @@ ablib:
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/crc32_gpu_$(VAR).o $(SRC)/crc32_gpu.hip
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/gpu_runtime_$(VAR).o $(SRC)/gpu_runtime.hip
 	$(CXX) $(CXXFLAGS) $(DEFS) -c -o $(BLD)/ab/crc_plan_$(VAR).o $(SRC)/crc_plan.cpp
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/probe_gpu.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o -lpthread
 
 # Same for the SHA-1 kernel: make ablib_sha1 VAR=name DEFS="-DCIO_SHA1_CHAINS=32"
 ablib_sha1:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/sha1_gpu_$(VAR).o $(SRC)/sha1_gpu.hip
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o -lpthread
 
-asm: $(SRC)/crc32_gpu.hip
+asm: $(BLD)/asm/crc32_gpu.s $(BLD)/asm/probe_gpu.s
+
+$(BLD)/asm/%.s: $(SRC)/%.hip $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
 	@mkdir -p $(BLD)/asm
-	$(HIPCC) $(HIPFLAGS) --offload-device-only -S -o $(BLD)/asm/crc32_gpu.s $<
+	$(HIPCC) $(HIPFLAGS) --offload-device-only -S -o $@ $<
 
 # The host planner under ASan + UBSan, stand-alone (no GPU, no HIP): the
 # shipped choices over the geometries of tests/test_plan_choice.py.

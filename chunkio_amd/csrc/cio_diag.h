@@ -7,64 +7,16 @@
  *
  * "Diagnostic" switches compute WRONG results on purpose (they remove work
  * to price it); they exist only to measure, never to ship.
+ *
+ * A switch whose question is answered is retired: its branch leaves the
+ * kernel and its entry leaves this file.  The CRC kernels' retired switches
+ * (and the paths they built) are in the history before the commit that added
+ * probe_gpu.hip; their results are in CHANGELOG.md, DESIGN.md and profiles/.
  */
 #ifndef CIO_DIAG_H
 #define CIO_DIAG_H
 
-/* ---- crc32_gpu.hip ------------------------------------------------------ */
-
-/* Diagnostic (round-3 probe, rejected): CIO_DIAG_RS_DYN compiles
- * read_stream_dyn_kernel, the read-only stream with a dynamically claimed
- * tail, selected at run time by CIO_GPU_RS_DYN="pool_permille,U,NC"
- * (tools/rs_dyn_probe.py; `make ablib VAR=rsdyn DEFS=-DCIO_DIAG_RS_DYN`).
- * Not in the product library. */
-
-/* Diagnostic: lanes read 16 slice / 4 shift table replicas instead of 32 / 8
- * (the 2-way bank conflicts of a two-workgroups-per-CU layout, priced at
- * today's occupancy).  Correct results, slower kernel. */
-#ifndef CIO_DIAG_HALF_REPLICAS
-#define CIO_DIAG_HALF_REPLICAS 0
-#endif
-
-/* Diagnostic: the stream kernel computes on register data instead of HBM
- * loads (compute-only time; wrong CRCs). */
-#ifndef CIO_ABLATE_LOADS
-#define CIO_ABLATE_LOADS 0
-#endif
-
-/* Diagnostic: skip the arrival/fold step of split chunks (prices the tail;
- * wrong CRCs for split chunks).  2: also skip the arrival descriptors' loads
- * at kernel start (prices their share of the start-up). */
-#ifndef CIO_DIAG_NO_ARRIVAL
-#define CIO_DIAG_NO_ARRIVAL 0
-#endif
-
-/* Diagnostic: 1 = finished waves stay resident ~5 us before exiting, 2 = they
- * wait for their workgroup (correct results). */
-#ifndef CIO_DIAG_TAIL
-#define CIO_DIAG_TAIL 0
-#endif
-
-/* A/B: chunks whose pieces all lie in one workgroup fold through LDS (1,
- * shipped) or through the global arrival counters (0). */
-#ifndef CIO_LDS_FOLD
-#define CIO_LDS_FOLD 1
-#endif
-
-/* A/B: the issue-ahead stream kernel peels each wave's last step off its
- * loop so that step issues no refill (1), or refills unconditionally (0). */
-#ifndef CIO_AHEAD_PEEL
-#define CIO_AHEAD_PEEL 1
-#endif
-
-/* Small-chunk kernel.  A/B: chunks in flight per wave (1 shipped, 2).
- * Diagnostic bit mask: 1 = no lane multiply, 2 = no LDS CRC (wrong CRCs). */
-#ifndef CIO_SMALL_SLOTS
-#define CIO_SMALL_SLOTS 1
-#endif
-#ifndef CIO_SMALL_EXP
-#define CIO_SMALL_EXP 0
-#endif
+/* ---- crc32_gpu.hip, crc_plan.cpp, gpu_runtime.hip ------------------------- */
 
 /* Alignment of a chunk's virtual start for chunks longer than one 4 KiB
  * step: 128 (one L2 line, shipped from round 5) or 16 (rounds 1-4).  At 128
@@ -77,15 +29,6 @@
  * (they stay on the small-chunk kernel). */
 #ifndef CIO_HEAD_ALIGN
 #define CIO_HEAD_ALIGN 128
-#endif
-
-/* Small-chunk kernel, L64 layout (CIO_GPU_L64=1): the lane's final multiply by
- * x^(8 * 64 (63 - L)) as 8 nibble-table lookups in the LDS the L64 layout
- * leaves free (the 32 KiB shift-table region: [nibble position j][nibble]
- * [lane] words, built per workgroup from the lane's register matrix) instead
- * of 32 bit-select + fused and-xor instructions. */
-#ifndef CIO_SMALL_NIBFOLD
-#define CIO_SMALL_NIBFOLD 0
 #endif
 
 /* ---- sha1_gpu.hip -------------------------------------------------------- */

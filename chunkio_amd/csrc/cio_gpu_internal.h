@@ -1,7 +1,8 @@
 // cio_gpu_internal.h -- declarations shared by the HIP translation units of
 // libchunkio_amd.so (gpu_runtime.hip: errors, device state, plans, rings;
-// crc32_gpu.hip: the CRC kernels and their launchers; devplan_gpu.hip: the
-// device planner; write_dev_gpu.hip: the write path of chunk images in HBM;
+// crc32_gpu.hip: the CRC kernels and their launchers; probe_gpu.hip: the
+// read-only stream and the synthetic fill; devplan_gpu.hip: the device
+// planner; write_dev_gpu.hip: the write path of chunk images in HBM;
 // host_pipeline.hip: the host-memory / file batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
 // planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.

@@ -34,19 +34,11 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <memory>
-#include <mutex>
-#include <shared_mutex>
-#include <vector>
-#include <string>
 #include <algorithm>
-
 #include <type_traits>
 
 #include "cio_gpu_internal.h"
+#include "crc_wave.h"
 
 using namespace cioa;
 
@@ -140,23 +132,8 @@ __device__ __forceinline__ uint32_t fold_full(const uint32_t (&s)[kSub])
     return h;
 }
 
-// floor(x / d) for x < 2^52, d >= 1: a correctly rounded double quotient is
-// within one of the integer quotient (x and d are exact in a double), and one
-// compare-and-step fixes it.  A 64-bit integer division is a ~120-instruction
-// SALU routine for wave-uniform operands; at kernel start 16 waves per CU
-// running three of them on the CU's one scalar unit delayed the last wave's
-// first HBM request by ~2.5 us.  This is ~20 VALU instructions per wave.
-__device__ __forceinline__ uint64_t div_u52(uint64_t x, uint64_t d)
-{
-    uint64_t q = (uint64_t) ((double) x / (double) d);
-    if (q * d > x) {
-        q -= 1;
-    } else if ((q + 1) * d <= x) {
-        q += 1;
-    }
-    return q;
-}
-
+// (The even split of wave-steps over the waves -- split_point, wave_start --
+// and wave_xor are in crc_wave.h.)
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
 {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t) v);
@@ -164,34 +141,8 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
     return ((uint64_t) hi << 32) | lo;
 }
 
-// floor(w * X / W), the even split of X units over W waves.  The plan
-// guarantees S < 2^40 and W <= 2^12 (plan_create), so w * X < 2^52.  A full
-// MI355X has W = 256 x 16 = 2^12 waves: then it is a uniform multiply and
-// shift on the scalar unit, and the kernels' first HBM requests wait on no
-// floating-point division.
-__device__ __forceinline__ uint64_t split_point(uint64_t w, uint64_t X, uint64_t W)
-{
-    if ((W & (W - 1)) == 0) {
-        return (w * X) >> __builtin_ctzll(W);
-    }
-    return div_u52(w * X, W);
-}
-
-__device__ __forceinline__ uint64_t wave_start(uint64_t w, uint64_t S, uint64_t W)
-{
-    return split_point(w, S, W);
-}
-
-// Replicas the lookups use: 32 slice / 8 shift.  Diagnostic build
-// (-DCIO_DIAG_HALF_REPLICAS): lanes read only 16 slice and 4 shift replicas
-// -- the tables a workgroup would hold in half the LDS (80 KiB, two
-// workgroups per CU) -- so every lookup group of 32 lanes takes the 2-way
-// bank conflicts such a layout has, at the current occupancy.
-#if CIO_DIAG_HALF_REPLICAS
-constexpr uint32_t kSliceRepMask = 15u, kShiftRepMask = 3u;
-#else
+// Replicas the lookups use: 32 slice / 8 shift.
 constexpr uint32_t kSliceRepMask = 31u, kShiftRepMask = 7u;
-#endif
 
 // Slice tables in LDS, replicated 32x so lane l always reads bank (l & 31):
 //   byte address(k, b, lane) = (k>>1)*65536 + b*256 + (k&1)*128 + (lane&31)*4
@@ -264,8 +215,6 @@ __device__ __forceinline__ uint32_t shift_block16(const char *lds, uint32_t lb_l
     return block16(lds, lb_lo, lb_hi, step_shift(lds, lrep, s), v);
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // Streaming loads: non-temporal (read once).  With the coalesced layout (a
 // wave-instruction reads 1 KiB contiguous) this is the fastest HBM read
 // policy measured on MI355X (tools/probe/crc_probe.hip).
@@ -329,7 +278,7 @@ __device__ __forceinline__ void table_entries(uint32_t k, uint32_t b, uint32_t &
 constexpr int kE = 1024 / kThreads;            // table entries per thread
 static_assert(kE == 1, "one slice and one shift entry per thread");
 
-template <bool STAMPS = false, bool SHIFT = true>
+template <bool STAMPS = false>
 __device__ __forceinline__ void write_tables(char *lds, uint32_t tid, const uint32_t (&tab_v)[kE],
                                              const uint32_t (&tab_sv)[kE], unsigned long long *ts = nullptr)
 {
@@ -340,13 +289,11 @@ __device__ __forceinline__ void write_tables(char *lds, uint32_t tid, const uint
     for (int i = 0; i < 8; ++i) {
         *reinterpret_cast<uint4 *>(lds + srow + 16u * ((lane + (uint32_t) i) & 7u)) = sv;
     }
-    if (SHIFT) {
-        const uint32_t hrow = kShiftOff + k * 8192u + b * 32u;
-        const uint4 hv = make_uint4(tab_sv[0], tab_sv[0], tab_sv[0], tab_sv[0]);
+    const uint32_t hrow = kShiftOff + k * 8192u + b * 32u;
+    const uint4 hv = make_uint4(tab_sv[0], tab_sv[0], tab_sv[0], tab_sv[0]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            *reinterpret_cast<uint4 *>(lds + hrow + 16u * ((lane + (uint32_t) i) & 1u)) = hv;
-        }
+    for (int i = 0; i < 2; ++i) {
+        *reinterpret_cast<uint4 *>(lds + hrow + 16u * ((lane + (uint32_t) i) & 1u)) = hv;
     }
     if (STAMPS) {
         ts[0] = __builtin_amdgcn_s_memrealtime();
@@ -371,14 +318,7 @@ __device__ __forceinline__ void load_step(StepRegs &r, const uint8_t *cbase, uin
     const uint64_t last = (vlen - 1) & ~15ull;
 #pragma unroll
     for (int q = 0; q < kSub; ++q) {
-#if CIO_ABLATE_LOADS
-        // Diagnostic build only: compute without HBM (wrong CRCs).
-        const uint64_t a = min(b0 + (uint64_t) q * kRow, last) + (uint64_t) (uintptr_t) cbase;
-        r.q[q] = make_uint4((uint32_t) a, (uint32_t) (a >> 7) * 0x9E3779B9u, (uint32_t) a ^ 0x5bd1e995u,
-                            (uint32_t) (a >> 3) + 0x7f4a7c15u);
-#else
         r.q[q] = ldg16(cbase + min(b0 + (uint64_t) q * kRow, last));
-#endif
     }
 }
 
@@ -554,21 +494,6 @@ __device__ __forceinline__ uint4 head_fix(uint4 v, uint32_t lane, uint32_t h, ui
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// XOR over the 64 lanes of a wave (every lane active), wave-uniform result.
-// DPP moves inside each 16-lane row (quad swaps, then the half-row and row
-// mirrors) leave every lane holding its row's XOR; four lane reads combine
-// the rows.  Plain VALU: __shfl_xor would be six ds_bpermute round trips
-// through the LDS pipe that the CRC lookups are using.
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-    v ^= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0xB1, 0xF, 0xF, false);    // quad_perm [1,0,3,2]
-    v ^= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x4E, 0xF, 0xF, false);    // quad_perm [2,3,0,1]
-    v ^= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x141, 0xF, 0xF, false);   // row_half_mirror
-    v ^= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x140, 0xF, 0xF, false);   // row_mirror
-    return (uint32_t) (__builtin_amdgcn_readlane((int) v, 0) ^ __builtin_amdgcn_readlane((int) v, 16) ^
-                       __builtin_amdgcn_readlane((int) v, 32) ^ __builtin_amdgcn_readlane((int) v, 48));
-}
-
 // A relaxed load at workgroup scope: a VECTOR load even for a uniform
 // address (an outstanding scalar load would force lgkmcnt(0) on every LDS
 // lookup of the CRC), counted in vmcnt with the ring's data loads.
@@ -668,7 +593,6 @@ __device__ __forceinline__ void rotate_prio(uint32_t slot_group, uint64_t it)
 // access.  The general path reads its WaveStart record first.  Separate
 // instantiations keep the general path's scalar-load wait out of the
 // uniform one's prologue.
-// (CIO_DIAG_NO_ARRIVAL, CIO_LDS_FOLD, CIO_DIAG_TAIL: cio_diag.h.)
 // AHEAD (uniform batches of whole 4 KiB steps with no alignment head: every
 // step is full, so the partial-step paths compile out): two ring slots, and
 // the next step's loads are issued as soon as this step's data has landed,
@@ -760,9 +684,10 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
 
     auto issue = [&](StepRegs &r) {
         // Past the wave's range the last step is re-read (cache-resident) so
-        // that every refill is the same 4 loads.  AHEAD refills past the
-        // range (its last one, or none when CIO_AHEAD_PEEL peels the last
-        // step) use a dummy source chosen branch-free, so one load sequence
+        // that every refill is the same 4 loads.  AHEAD refills nothing past
+        // the range (the wave's last step is peeled off its loop); its only
+        // issue without a step, the first one of a wave with an empty range,
+        // uses a dummy source chosen branch-free, so one load sequence
         // serves every path and the compiler's vmcnt waits stay exact: in a
         // uniform batch chunk 0's first step at base + ua0 (both preloaded
         // SGPRs -- the slice-table pointer is a kernel argument the hardware
@@ -778,12 +703,12 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
                 load_step(r, src, real ? lj : 0, real ? ld.vlen : (uint64_t) kStep, lane);
             }
         } else {
-        const uint64_t jj = nload > 0 ? lj : (uint64_t) ld.nsteps - 1;
-        if (L64) {
-            load_step64c(r, lbase + ld.a, jj, ld.vlen, lane);
-        } else {
-            load_step(r, lbase + ld.a, jj, ld.vlen, lane);
-        }
+            const uint64_t jj = nload > 0 ? lj : (uint64_t) ld.nsteps - 1;
+            if (L64) {
+                load_step64c(r, lbase + ld.a, jj, ld.vlen, lane);
+            } else {
+                load_step(r, lbase + ld.a, jj, ld.vlen, lane);
+            }
         }
         if (nload > 0) {
             --nload;
@@ -827,16 +752,9 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
     // Descriptors of the first 64 chunks from c0 (one per lane) for the
     // arrival step at the end; fetched now so that they cost nothing there.
     // Clamped, not predicated: a branch would break the ring's vmcnt tracking.
-    uint64_t ar_g = 0;
-    uint32_t ar_ns = 0, ar_np = 0, ar_w0 = 0, ar_w1 = 0;
-    if (CIO_DIAG_NO_ARRIVAL < 2) {
-        const ChunkDesc &ad = desc[min(c0 + lane, n - 1)];
-        ar_g = ad.g;
-        ar_ns = ad.nsteps;
-        ar_np = ad.npieces;
-        ar_w0 = ad.w0;
-        ar_w1 = ad.w1;
-    }
+    const ChunkDesc &ad0 = desc[min(c0 + lane, n - 1)];
+    uint64_t ar_g = ad0.g;
+    uint32_t ar_ns = ad0.nsteps, ar_np = ad0.npieces, ar_w0 = ad0.w0, ar_w1 = ad0.w1;
     // Fold factor of a piece that ends with a full step (the common case):
     // sub-chain q of lane l then ends 1024 (3 - q) + 16 (63 - l) bytes before
     // the piece end.  The 1024 (3 - q) parts are compile-time constants
@@ -856,7 +774,7 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
     // SGPR right here, and that wait (vmcnt, in order) would hold the table
     // build until the first step's data had landed.
     const uint32_t *wwords = pfac + (W + n + 1);
-    const uint32_t wfl = CIO_LDS_FOLD ? load_lane_u32(wwords + wave) : 0u;
+    const uint32_t wfl = load_lane_u32(wwords + wave);
     const uint32_t wlast = load_lane_u32(wwords + W + wave);
     uint32_t fold_own = 0, pub = 0;
     // Keep the scheduler from sinking these loads below the table build (and
@@ -885,130 +803,124 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
         // range end); the piece is published by piece_end() after the next
         // step's loads are issued, so their latency overlaps the fold.
         auto crc_step = [&](StepRegs &r) -> bool {
-            {
-                if (L64 && (AHEAD || j < full_end)) {
-                    // one chain per lane: jump 4032 bytes, then 64 contiguous bytes
-                    const uint32_t h0 = step_shift(lds, lrep, s[0]);
-                    transpose64(r);
-                    if (j == 0) {
-                        if (AHEAD) {
-                            r.q[0].x ^= lane == 0 ? seed : 0u;   // h = 0: the seed on content bytes 0..3
-                        } else {
-                            // head bytes and seed: granules 0 and 1 of lane 0 (4 L + k);
-                            // with 128-byte heads, granules 0..8 (lanes 0..2)
-                            r.q[0] = head_fix(r.q[0], 4u * lane, d.h, seed);
-                            r.q[1] = head_fix(r.q[1], 4u * lane + 1u, d.h, seed);
-                            if (CIO_HEAD_ALIGN > 16) {
-                                r.q[2] = head_fix(r.q[2], 4u * lane + 2u, d.h, seed);
-                                r.q[3] = head_fix(r.q[3], 4u * lane + 3u, d.h, seed);
-                            }
+            if (L64 && (AHEAD || j < full_end)) {
+                // one chain per lane: jump 4032 bytes, then 64 contiguous bytes
+                const uint32_t h0 = step_shift(lds, lrep, s[0]);
+                transpose64(r);
+                if (j == 0) {
+                    if (AHEAD) {
+                        r.q[0].x ^= lane == 0 ? seed : 0u;   // h = 0: the seed on content bytes 0..3
+                    } else {
+                        // head bytes and seed: granules 0 and 1 of lane 0 (4 L + k);
+                        // with 128-byte heads, granules 0..8 (lanes 0..2)
+                        r.q[0] = head_fix(r.q[0], 4u * lane, d.h, seed);
+                        r.q[1] = head_fix(r.q[1], 4u * lane + 1u, d.h, seed);
+                        if (CIO_HEAD_ALIGN > 16) {
+                            r.q[2] = head_fix(r.q[2], 4u * lane + 2u, d.h, seed);
+                            r.q[3] = head_fix(r.q[3], 4u * lane + 3u, d.h, seed);
                         }
                     }
-                    uint32_t st = block16(lds, lb_lo, lb_hi, h0, r.q[0]);
-#pragma unroll
-                    for (int q = 1; q < kSub; ++q) {
-                        st = block16(lds, lb_lo, lb_hi, st, r.q[q]);
-                    }
-                    s[0] = st;
-                    if (!AHEAD) {
-                        e[0] = (uint64_t) j * kStep + 64ull * (lane + 1);
-                    }
-                } else if (L64) {
-                    transpose64(r);
-                    slow_compute64(lds, lb_lo, lb_hi, lrep, r, j, d.vlen, d.h, seed, lane, s[0], e[0]);
-                } else if (AHEAD || j < full_end) {
-                    // The 4080-byte jump of every sub-chain needs only its
-                    // state: its lookups go out before the first use of the
-                    // step's data, so after the data lands only the four
-                    // rounds of the 16-byte update remain.
-                    uint32_t h[kSub];
-#pragma unroll
-                    for (int q = 0; q < kSub; ++q) {
-                        h[q] = step_shift(lds, lrep, s[q]);
-                    }
-                    if (j == 0) {
-                        r.q[0] = head_fix(r.q[0], lane, d.h, seed);
-                    }
-#pragma unroll
-                    for (int q = 0; q < kSub; ++q) {
-                        s[q] = block16(lds, lb_lo, lb_hi, h[q], r.q[q]);
-                    }
-                    if (!AHEAD) {
-                        const uint64_t e0 = (uint64_t) j * kStep + (uint64_t) (lane + 1) * kGran;
-#pragma unroll
-                        for (int q = 0; q < kSub; ++q) {
-                            e[q] = e0 + (uint64_t) q * kRow;
-                        }
-                    }
-                } else {
-                    slow_compute(lds, lb_lo, lb_hi, lrep, r, j, d.vlen, d.h, seed, lane, s, e);
                 }
-                ++g;
-                ++j;
-                return j == d.nsteps || g == gend;
+                uint32_t st = block16(lds, lb_lo, lb_hi, h0, r.q[0]);
+#pragma unroll
+                for (int q = 1; q < kSub; ++q) {
+                    st = block16(lds, lb_lo, lb_hi, st, r.q[q]);
+                }
+                s[0] = st;
+                if (!AHEAD) {
+                    e[0] = (uint64_t) j * kStep + 64ull * (lane + 1);
+                }
+            } else if (L64) {
+                transpose64(r);
+                slow_compute64(lds, lb_lo, lb_hi, lrep, r, j, d.vlen, d.h, seed, lane, s[0], e[0]);
+            } else if (AHEAD || j < full_end) {
+                // The 4080-byte jump of every sub-chain needs only its
+                // state: its lookups go out before the first use of the
+                // step's data, so after the data lands only the four
+                // rounds of the 16-byte update remain.
+                uint32_t h[kSub];
+#pragma unroll
+                for (int q = 0; q < kSub; ++q) {
+                    h[q] = step_shift(lds, lrep, s[q]);
+                }
+                if (j == 0) {
+                    r.q[0] = head_fix(r.q[0], lane, d.h, seed);
+                }
+#pragma unroll
+                for (int q = 0; q < kSub; ++q) {
+                    s[q] = block16(lds, lb_lo, lb_hi, h[q], r.q[q]);
+                }
+                if (!AHEAD) {
+                    const uint64_t e0 = (uint64_t) j * kStep + (uint64_t) (lane + 1) * kGran;
+#pragma unroll
+                    for (int q = 0; q < kSub; ++q) {
+                        e[q] = e0 + (uint64_t) q * kRow;
+                    }
+                }
+            } else {
+                slow_compute(lds, lb_lo, lb_hi, lrep, r, j, d.vlen, d.h, seed, lane, s, e);
             }
+            ++g;
+            ++j;
+            return j == d.nsteps || g == gend;
         };
         // Piece end: shift every sub-chain state to the piece end, reduce over
         // the wave, publish (write-through, agent scope), move to the next chunk.
         auto piece_end = [&]() {
-            {
-                {
-                    uint32_t contrib;
-                    if (AHEAD || j <= full_end) {
-                        // The last step was full: Horner over the sub-chains
-                        // with the constant x^(8 * 1024), then the lane factor.
-                        // (The asm keeps the compiler from hoisting xl's 32
-                        // bit masks out of the loop into 64 spilled SGPRs.)
-                        // A non-final piece (the range's last) takes F instead
-                        // of the lane factor, landing at the chunk end.
-                        uint32_t a = j < d.nsteps ? xlast : xl;
-                        asm volatile("" : "+v"(a));
-                        contrib = multmodp(a, L64 ? s[0] : fold_full<UNIFORM>(s));
-                    } else {
-                        const uint64_t pend = min((uint64_t) j * kStep, d.vlen);
-                        contrib = 0;
+            uint32_t contrib;
+            if (AHEAD || j <= full_end) {
+                // The last step was full: Horner over the sub-chains
+                // with the constant x^(8 * 1024), then the lane factor.
+                // (The asm keeps the compiler from hoisting xl's 32
+                // bit masks out of the loop into 64 spilled SGPRs.)
+                // A non-final piece (the range's last) takes F instead
+                // of the lane factor, landing at the chunk end.
+                uint32_t a = j < d.nsteps ? xlast : xl;
+                asm volatile("" : "+v"(a));
+                contrib = multmodp(a, L64 ? s[0] : fold_full<UNIFORM>(s));
+            } else {
+                const uint64_t pend = min((uint64_t) j * kStep, d.vlen);
+                contrib = 0;
 #pragma unroll
-                        for (int q = 0; q < kSub; ++q) {
-                            const uint64_t dist = e[q] < pend ? pend - e[q] : 0;
-                            contrib ^= s[q] ? multmodp(g_x8[min(dist, (uint64_t) (kX8Count - 1))], s[q]) : 0u;
-                        }
-                    }
-                    contrib = wave_xor(contrib);
-                    if (d.g >= g0 && j == d.nsteps) {
-                        // The whole chunk lies in this wave's range: the piece
-                        // is the chunk's CRC (no partial slot, no arrival).
-                        if (lane == 0) {
-                            out[cid ? cid[c] : c] = contrib;
-                        }
-                    } else if (j == d.nsteps && (wfl & kWfFold)) {
-                        fold_own = contrib;    // the final piece of c0 (== c)
-                    } else if (j < d.nsteps && (wfl & kWfPublish)) {
-                        pub = contrib;         // the range ends inside a local chunk
-                    } else {
-                        __hip_atomic_store(&partials[(uint64_t) wave + c], (unsigned long long) contrib,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    if (g < gend) {
-                        if (UNIFORM) {
-                            ++c;
-                            d.a += ustride;
-                            d.g += unsteps;
-                        } else {
-                            do {
-                                ++c;
-                                d = desc[c];
-                            } while (d.nsteps == 0);
-                        }
-                        j = 0;
-#pragma unroll
-                        for (int q = 0; q < kSub; ++q) {
-                            s[q] = 0u;
-                            e[q] = 0ull;
-                        }
-                        full_end = (uint32_t) (d.vlen / kStep);
-                        seed = seeds ? seeds[cid ? cid[c] : c] : 0xffffffffu;
-                    }
+                for (int q = 0; q < kSub; ++q) {
+                    const uint64_t dist = e[q] < pend ? pend - e[q] : 0;
+                    contrib ^= s[q] ? multmodp(g_x8[min(dist, (uint64_t) (kX8Count - 1))], s[q]) : 0u;
                 }
+            }
+            contrib = wave_xor(contrib);
+            if (d.g >= g0 && j == d.nsteps) {
+                // The whole chunk lies in this wave's range: the piece
+                // is the chunk's CRC (no partial slot, no arrival).
+                if (lane == 0) {
+                    out[cid ? cid[c] : c] = contrib;
+                }
+            } else if (j == d.nsteps && (wfl & kWfFold)) {
+                fold_own = contrib;    // the final piece of c0 (== c)
+            } else if (j < d.nsteps && (wfl & kWfPublish)) {
+                pub = contrib;         // the range ends inside a local chunk
+            } else {
+                __hip_atomic_store(&partials[(uint64_t) wave + c], (unsigned long long) contrib,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (g < gend) {
+                if (UNIFORM) {
+                    ++c;
+                    d.a += ustride;
+                    d.g += unsteps;
+                } else {
+                    do {
+                        ++c;
+                        d = desc[c];
+                    } while (d.nsteps == 0);
+                }
+                j = 0;
+#pragma unroll
+                for (int q = 0; q < kSub; ++q) {
+                    s[q] = 0u;
+                    e[q] = 0ull;
+                }
+                full_end = (uint32_t) (d.vlen / kStep);
+                seed = seeds ? seeds[cid ? cid[c] : c] : 0xffffffffu;
             }
         };
 
@@ -1064,7 +976,6 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
                 }
             };
             using Refill = std::true_type;
-#if CIO_AHEAD_PEEL
             // The wave's last step is peeled off the loop: it issues no
             // refill, so the wave does not end waiting for four loads nobody
             // reads (the refill past the range re-reads the slice table; its
@@ -1081,39 +992,32 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
             } else if (iters - it == 1) {
                 half(it, cur, nxt, NoRefill());
             }
-#else
-            for (uint64_t it = 0; it < iters; it += 2) {
-                half(it, cur, nxt, Refill());
-                if (it + 1 < iters) {
-                    half(it + 1, nxt, cur, Refill());
+        } else {
+            for (uint64_t it = 0; it < iters; ++it) {
+                if (PRIO) {
+                    rotate_prio(slot_group, it);
                 }
-            }
-#endif
-        }
-        for (uint64_t it = 0; !AHEAD && it < iters; ++it) {
-            if (PRIO) {
-                rotate_prio(slot_group, it);
-            }
-            if (it == it_f) {
-                // (The asm keeps the compiler from hoisting the multiply to
-                // the loop's preheader, where it waited for these loads and
-                // delayed every wave's first step.)
-                uint32_t wl = wlast;
-                asm volatile("" : "+v"(wl));
-                xlast = multmodp(wl, xl);
-            }
-            const bool pe = crc_step(cur);
-            if (STAMPS && it == 0) {
-                t_step1 = __builtin_amdgcn_s_memrealtime();
-            }
-            if (nload > 0) {
-                issue(cur);
-            }
-            if (pe) {
-                piece_end();
-            }
-            if (STAMPS && it == iters / 2) {
-                t_mid = __builtin_amdgcn_s_memrealtime();
+                if (it == it_f) {
+                    // (The asm keeps the compiler from hoisting the multiply to
+                    // the loop's preheader, where it waited for these loads and
+                    // delayed every wave's first step.)
+                    uint32_t wl = wlast;
+                    asm volatile("" : "+v"(wl));
+                    xlast = multmodp(wl, xl);
+                }
+                const bool pe = crc_step(cur);
+                if (STAMPS && it == 0) {
+                    t_step1 = __builtin_amdgcn_s_memrealtime();
+                }
+                if (nload > 0) {
+                    issue(cur);
+                }
+                if (pe) {
+                    piece_end();
+                }
+                if (STAMPS && it == iters / 2) {
+                    t_mid = __builtin_amdgcn_s_memrealtime();
+                }
             }
         }
         if (PRIO) {
@@ -1132,13 +1036,13 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
         // chunks were written out directly); the batch of 64 ends the scan
         // if it reaches a non-empty chunk that starts past the range (or the
         // end of the batch).
-        for (uint32_t ac = c0; !CIO_DIAG_NO_ARRIVAL;) {
+        for (uint32_t ac = c0;;) {
             const uint32_t idx = ac + lane;
             const bool inb = idx < n;
             const bool whole = ar_g >= g0 && ar_g + ar_ns <= gend;
             // Workgroup-local chunks (first and last piece in one workgroup)
             // were folded through LDS.
-            const bool local = CIO_LDS_FOLD && (ar_w0 ^ ar_w1) < kWavesPerWg;
+            const bool local = (ar_w0 ^ ar_w1) < kWavesPerWg;
             const bool member = inb && ar_ns != 0 && ar_g < gend && !whole && !local;
             const bool stop = !inb || (ar_ns != 0 && ar_g >= gend);
             uint32_t old = 0;
@@ -1168,47 +1072,36 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
         t_arrived = __builtin_amdgcn_s_memrealtime();
     }
     tiny_chunks(lds, lb_lo, base, desc, tiny, seeds, out, cid, ntiny, wave, lane, W);
-    if (CIO_LDS_FOLD) {
-        // Every wave is past its last table lookup: the LDS words are free.
-        __syncthreads();
-        if (STAMPS) {
-            t_bar1 = __builtin_amdgcn_s_memrealtime();
+    // The workgroup-local fold.  Every wave is past its last table lookup:
+    // the LDS words are free.
+    __syncthreads();
+    if (STAMPS) {
+        t_bar1 = __builtin_amdgcn_s_memrealtime();
+    }
+    uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
+    if (lane == 0) {
+        slot[tid >> 6] = pub;    // 0 unless the range ended inside a local chunk
+    }
+    __syncthreads();
+    if (STAMPS) {
+        t_bar2 = __builtin_amdgcn_s_memrealtime();
+    }
+    if (wfl & kWfFold) {
+        // Lane i < 16 <-> wave (wave - 16 + i); the nb waves before this
+        // one hold the chunk's earlier pieces (empty ranges published 0).
+        const uint32_t nb = (wfl >> 8) & 0xffu;
+        uint32_t a = 0;
+        if (lane < kWavesPerWg && lane >= kWavesPerWg - nb) {
+            a = slot[(tid >> 6) + lane - kWavesPerWg];
         }
-        uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
+        a = wave_xor(a) ^ fold_own;
         if (lane == 0) {
-            slot[tid >> 6] = pub;    // 0 unless the range ended inside a local chunk
-        }
-        __syncthreads();
-        if (STAMPS) {
-            t_bar2 = __builtin_amdgcn_s_memrealtime();
-        }
-        if (wfl & kWfFold) {
-            // Lane i < 16 <-> wave (wave - 16 + i); the nb waves before this
-            // one hold the chunk's earlier pieces (empty ranges published 0).
-            const uint32_t nb = (wfl >> 8) & 0xffu;
-            uint32_t a = 0;
-            if (lane < kWavesPerWg && lane >= kWavesPerWg - nb) {
-                a = slot[(tid >> 6) + lane - kWavesPerWg];
-            }
-            a = wave_xor(a) ^ fold_own;
-            if (lane == 0) {
-                out[cid ? cid[c0] : c0] = a;
-            }
-        }
-        if (STAMPS) {
-            t_folded = __builtin_amdgcn_s_memrealtime();
+            out[cid ? cid[c0] : c0] = a;
         }
     }
-#if CIO_DIAG_TAIL == 1
-    {   // diagnostic: finished waves stay resident ~5 us (sleeping) before exiting
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__builtin_amdgcn_s_memrealtime() - t0 < 500) {
-            __builtin_amdgcn_s_sleep(10);
-        }
+    if (STAMPS) {
+        t_folded = __builtin_amdgcn_s_memrealtime();
     }
-#elif CIO_DIAG_TAIL == 2
-    __syncthreads();   // diagnostic: finished waves wait for the workgroup before exiting
-#endif
     if (STAMPS && lane == 0) {
         // Diagnostic build only: 100 MHz global clock, per wave.
         uint32_t hw_id, xcc_id;
@@ -1255,58 +1148,11 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
 // ring refill is the same loads (4 data rows; the un-shift factor unless the
 // batch is uniform; the seed when seeds are given), so the compiler's vmcnt
 // waits are exact.
-// (CIO_SMALL_SLOTS, CIO_SMALL_EXP: cio_diag.h.)
 struct SmallRegs {
     uint4 q[kSub];
     uint32_t inv;    // x^(-8 D), D = 4096 - virtual length
     uint32_t seed;   // the chunk's seed
 };
-
-
-// CIO_SMALL_NIBFOLD (cio_diag.h): M_L s for the lane's matrix M_L as 8 nibble
-// lookups.  Table layout in the shift-table region: word (j, nib, lane) at
-// kShiftOff + j * 4096 + nib * 256 + lane * 4 = M_L (nib << 4 j), so the 32
-// lanes of a half-wave read 32 different banks whatever the nibbles.
-// Wave w of the workgroup writes nibble position j = w / 2, nibbles
-// 8 (w & 1) .. + 8, from columns 4 j .. 4 j + 3 of its lanes' matrices.
-template <int J>
-__device__ __forceinline__ void nib_rows(char *lds, uint32_t lane4, const uint32_t (&col)[32], uint32_t half)
-{
-    const uint32_t c0 = col[4 * J], c1 = col[4 * J + 1], c2 = col[4 * J + 2];
-    const uint32_t c3 = col[4 * J + 3] & (0u - half);
-    char *t = lds + kShiftOff + (uint32_t) J * 4096u + half * 2048u + lane4;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t v = ((k & 1) ? c0 : 0u) ^ ((k & 2) ? c1 : 0u) ^ ((k & 4) ? c2 : 0u) ^ c3;
-        *reinterpret_cast<uint32_t *>(t + (uint32_t) k * 256u) = v;
-    }
-}
-
-__device__ __forceinline__ void write_nib_tables(char *lds, uint32_t tid, const uint32_t (&col)[32])
-{
-    const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6), lane4 = (tid & 63u) << 2, half = w & 1u;
-    switch (w >> 1) {
-    case 0: nib_rows<0>(lds, lane4, col, half); break;
-    case 1: nib_rows<1>(lds, lane4, col, half); break;
-    case 2: nib_rows<2>(lds, lane4, col, half); break;
-    case 3: nib_rows<3>(lds, lane4, col, half); break;
-    case 4: nib_rows<4>(lds, lane4, col, half); break;
-    case 5: nib_rows<5>(lds, lane4, col, half); break;
-    case 6: nib_rows<6>(lds, lane4, col, half); break;
-    default: nib_rows<7>(lds, lane4, col, half); break;
-    }
-}
-
-__device__ __forceinline__ uint32_t nib_fold(const char *lds, uint32_t lane4, uint32_t s)
-{
-    const char *t = lds + kShiftOff + lane4;
-    uint32_t v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        v[j] = *reinterpret_cast<const uint32_t *>(t + (uint32_t) j * 4096u + ((s >> (4 * j)) & 15u) * 256u);
-    }
-    return xor3(xor3(v[0], v[1], v[2]), xor3(v[3], v[4], v[5]), v[6] ^ v[7]);
-}
 
 // Zero the bytes of a 16-byte block at virtual offset bs past the end v.
 __device__ __forceinline__ uint4 mask_tail(uint4 v, uint32_t bs, uint32_t vlen)
@@ -1393,14 +1239,8 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
         }
     };
 
-#if CIO_SMALL_SLOTS == 2
-    SmallRegs ra, rb;
-    issue(ra, c0);
-    issue(rb, c0 + 1);
-#else
     SmallRegs cur;
     issue(cur, c0);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // x^(8 * 16 (63 - l)): the lane's fold factor (the register matrix below
     // waits for it), requested right behind the first data.
@@ -1416,8 +1256,7 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
         table_entries<cx_xpow8n(kRow - kGran)>(__builtin_amdgcn_readfirstlane(idx >> 8), idx & 255u,
                                                tab_v[e], tab_sv[e]);
     }
-    constexpr bool kNib = L64 && CIO_SMALL_NIBFOLD;
-    write_tables<false, !kNib>(lds, tid, tab_v, tab_sv);
+    write_tables(lds, tid, tab_v, tab_sv);
     // The multiply by xl as a 32 x 32 GF(2) matrix held in registers: column
     // j = xl * x^(31 - j) (reflected bit j).
     uint32_t col[32];
@@ -1425,9 +1264,6 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
 #pragma unroll
     for (int j = 30; j >= 0; --j) {
         col[j] = (col[j + 1] >> 1) ^ (CIOA_POLY & (0u - (col[j + 1] & 1u)));
-    }
-    if (kNib) {
-        write_nib_tables(lds, tid, col);
     }
     // Uniform batch without seeds: the head granule's fix-up (clear the bytes
     // before the content, XOR the initial 0xffffffff in) is the same for every
@@ -1488,19 +1324,12 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
                                        vlen);
                 }
             }
-            if (CIO_SMALL_EXP & 2) {
+            // (the chain starts at 0: its first block needs no jump)
+            st = block16(lds, lb_lo, lb_hi, 0u, r.q[0]);
 #pragma unroll
-                for (int q = 0; q < kSub; ++q) {
-                    st ^= r.q[q].x ^ r.q[q].y ^ r.q[q].z ^ r.q[q].w;
-                }
-            } else {
-                // (the chain starts at 0: its first block needs no jump)
-                st = block16(lds, lb_lo, lb_hi, 0u, r.q[0]);
-#pragma unroll
-                for (int q = 1; q < kSub; ++q) {
-                    st = L64 ? block16(lds, lb_lo, lb_hi, st, r.q[q])
-                             : shift_block16(lds, lb_lo, lb_hi, lrep, st, r.q[q]);
-                }
+            for (int q = 1; q < kSub; ++q) {
+                st = L64 ? block16(lds, lb_lo, lb_hi, st, r.q[q])
+                         : shift_block16(lds, lb_lo, lb_hi, lrep, st, r.q[q]);
             }
         }
         uint32_t inv = inv_u;
@@ -1508,18 +1337,13 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
             asm volatile("v_mov_b32 %0, %1" : "=v"(inv) : "v"(cur.inv));
         }
         // The next chunk's loads go out before the fold.
-        issue(cur, c + CIO_SMALL_SLOTS);
+        issue(cur, c + 1);
         if (live) {
-            uint32_t x = st;
-            if (kNib && !(CIO_SMALL_EXP & 1)) {
-                x = nib_fold(lds, lane << 2, st);
-            } else if (!(CIO_SMALL_EXP & 1)) {
-                // 32 x (bit-field sign extend, fused and-xor)
-                x = col[0] & (0u - (st & 1u));
+            // 32 x (bit-field sign extend, fused and-xor)
+            uint32_t x = col[0] & (0u - (st & 1u));
 #pragma unroll
-                for (int j = 1; j < 32; ++j) {
-                    x = xor_and(x, 0u - ((st >> j) & 1u), col[j]);
-                }
+            for (int j = 1; j < 32; ++j) {
+                x = xor_and(x, 0u - ((st >> j) & 1u), col[j]);
             }
             uint32_t crc = wave_xor(x);
             if (vlen != (uint32_t) kStep) {
@@ -1531,12 +1355,6 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
             }
         }
     };
-#if CIO_SMALL_SLOTS == 2
-    for (uint32_t c = c0; c < c1; c += 2) {
-        chunk(ra, c);
-        chunk(rb, c + 1);
-    }
-#else
     // Issue priority rotates per chunk as in the stream kernel, so no wave of
     // a SIMD stays behind its mates under the age tie-break (cfg4k 68.7 ->
     // 66.6 us back to back, profiles/r02/ab_small_prio_rotation.txt).
@@ -1546,286 +1364,8 @@ crc32_small_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint64_t
         chunk(cur, c);
     }
     __builtin_amdgcn_s_setprio(0);
-#endif
     tiny_chunks(lds, lb_lo, base, desc, tiny, seeds, out, nullptr, ntiny, wave, lane, W);
 }
-
-// ---------------------------------------------------------------- read-only stream
-
-// Practical HBM-read ceiling for the CRC kernel's access pattern: the same
-// persistent grid (one 1024-thread workgroup per CU), the same even split of
-// 4 KiB wave-steps and the same coalesced non-temporal 16-byte loads, with the
-// CRC replaced by an XOR.  One 4-byte store per wave keeps the loads live.
-__global__ void __launch_bounds__(kThreads, 1)
-read_stream_kernel(const uint8_t *__restrict__ base, uint64_t S, uint32_t *__restrict__ sink, uint32_t B,
-                   unsigned long long *stamps, uint32_t work)
-{
-    const unsigned long long t_entry = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-    unsigned long long t_first = 0;
-    const uint32_t W = gridDim.x * (kThreads / kWave);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kThreads / kWave) + (threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
-    u32x4 acc = {0u, 0u, 0u, 0u};
-    // diagnostic (CIO_GPU_RS_WORK=n): n rounds of 4 independent dependent
-    // chains of full-rate VALU work (3 instructions per chain and round) on
-    // each step's data, standing in for the CRC's arithmetic.
-    auto burn = [&]() {
-        uint32_t x0 = acc.x, x1 = acc.y, x2 = acc.z, x3 = acc.w;
-        for (uint32_t k = 0; k < work; ++k) {
-            x0 = __builtin_amdgcn_alignbit(x0, x0, 27) ^ (x0 + k);
-            x1 = __builtin_amdgcn_alignbit(x1, x1, 27) ^ (x1 + k);
-            x2 = __builtin_amdgcn_alignbit(x2, x2, 27) ^ (x2 + k);
-            x3 = __builtin_amdgcn_alignbit(x3, x3, 27) ^ (x3 + k);
-        }
-        acc = u32x4{x0, x1, x2, x3};
-    };
-    // diagnostic (CIO_GPU_RS_LANE): lane l reads 32 or 64 contiguous bytes of
-    // each half / whole step (2 or 4 dwordx4 loads at a 32 / 64-byte lane
-    // stride) instead of 16 bytes of each 1 KiB row.
-    const uint32_t lsh = work >> 16;
-    work &= 0xffffu;
-    auto step = [&](uint64_t g) {
-        if (lsh == 0) {
-            const u32x4 *p = reinterpret_cast<const u32x4 *>(base + g * kStep + (uint64_t) lane * kGran);
-#pragma unroll
-            for (int q = 0; q < kSub; ++q) {
-                acc ^= __builtin_nontemporal_load(p + q * kWave);
-            }
-        } else if (lsh == 1) {
-            const u32x4 *p = reinterpret_cast<const u32x4 *>(base + g * kStep + (uint64_t) lane * 32u);
-            acc ^= __builtin_nontemporal_load(p);
-            acc ^= __builtin_nontemporal_load(p + 1);
-            acc ^= __builtin_nontemporal_load(p + 128);
-            acc ^= __builtin_nontemporal_load(p + 129);
-        } else {
-            const u32x4 *p = reinterpret_cast<const u32x4 *>(base + g * kStep + (uint64_t) lane * 64u);
-#pragma unroll
-            for (int q = 0; q < kSub; ++q) {
-                acc ^= __builtin_nontemporal_load(p + q);
-            }
-        }
-        burn();
-    };
-    if (B == 0xffffffffu) {
-        // diagnostic (CIO_GPU_RS_BLOCK=-1): the contiguous split with two
-        // steps in flight per wave (the last two refills re-read the last step)
-        const uint64_t g0 = wave_start(wave, S, W), g1 = wave_start((uint64_t) wave + 1, S, W);
-        if (g0 < g1) {
-            auto ld4 = [&](u32x4 *r, uint64_t g) {
-                const u32x4 *p = reinterpret_cast<const u32x4 *>(base + min(g, g1 - 1) * kStep +
-                                                                 (uint64_t) lane * kGran);
-#pragma unroll
-                for (int q = 0; q < kSub; ++q) {
-                    r[q] = __builtin_nontemporal_load(p + q * kWave);
-                }
-            };
-            u32x4 ra[kSub], rb[kSub];
-            ld4(ra, g0);
-            ld4(rb, g0 + 1);
-            for (uint64_t g = g0; g < g1; g += 2) {
-#pragma unroll
-                for (int q = 0; q < kSub; ++q) {
-                    acc ^= ra[q];
-                }
-                ld4(ra, g + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                burn();
-#pragma unroll
-                for (int q = 0; q < kSub; ++q) {
-                    acc ^= rb[q];
-                }
-                ld4(rb, g + 3);
-                __builtin_amdgcn_sched_barrier(0);
-                burn();
-            }
-        }
-    } else if (B & 0x80000000u) {
-        // diagnostic (CIO_GPU_RS_WGPOOL=k): the CRC kernel's split, but the
-        // last k steps of every wave's range form a workgroup pool that the
-        // workgroup's waves claim one step at a time (LDS atomic) once their
-        // own ranges are done: intra-workgroup balancing, priced on the
-        // read-only stream.
-        __shared__ uint32_t pool_next;
-        const uint32_t k = B & 0xffffu;
-        if (threadIdx.x == 0) {
-            pool_next = 0;
-        }
-        __syncthreads();
-        auto static_end = [&](uint64_t w, uint64_t &e1) {
-            const uint64_t a = wave_start(w, S, W), b = wave_start(w + 1, S, W);
-            e1 = b;
-            return b > a + k ? b - k : a;
-        };
-        uint64_t g1;
-        const uint64_t g0 = wave_start(wave, S, W), gs = static_end(wave, g1);
-        for (uint64_t g = g0; g < gs; ++g) {
-            step(g);
-        }
-        const uint32_t first = blockIdx.x * (kThreads / kWave);
-        for (;;) {
-            uint32_t item = 0;
-            if (lane == 0) {
-                item = atomicAdd(&pool_next, 1u);
-            }
-            item = __builtin_amdgcn_readfirstlane(item);
-            if (item >= (kThreads / kWave) * k) {
-                break;
-            }
-            uint64_t o1;
-            const uint64_t os = static_end(first + item / k, o1);
-            const uint64_t g = os + item % k;
-            if (g < o1) {
-                step(g);
-            }
-        }
-    } else if (B == 0) {
-        // the CRC kernel's split: one contiguous range per wave
-        const uint64_t g0 = wave_start(wave, S, W), g1 = wave_start((uint64_t) wave + 1, S, W);
-        for (uint64_t g = g0; g < g1; ++g) {
-            step(g);
-            if (stamps && g == g0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                t_first = __builtin_amdgcn_s_memrealtime();
-            }
-        }
-    } else {
-        // diagnostic (CIO_GPU_RS_BLOCK=B): blocks of B steps dealt round-robin over the waves
-        for (uint64_t b = wave; b * B < S; b += W) {
-            for (uint64_t g = b * B; g < min(S, b * B + B); ++g) {
-                step(g);
-            }
-        }
-    }
-    const uint32_t x = wave_xor(acc[0] ^ acc[1] ^ acc[2] ^ acc[3]);
-    if (lane == 0) {
-        sink[wave] = x;
-    }
-    if (stamps && lane == 0) {
-        // Diagnostic (CIO_GPU_RS_STAMPS=1): 100 MHz global clock, per wave.
-        uint32_t xcc_id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
-        stamps[4 * wave + 0] = t_entry;
-        stamps[4 * wave + 1] = t_first;
-        stamps[4 * wave + 2] = __builtin_amdgcn_s_memrealtime();
-        stamps[4 * wave + 3] = xcc_id;
-    }
-}
-
-// ---------------------------------------------------------------- synthetic fill
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__global__ void __launch_bounds__(256)
-fill_kernel(uint8_t *__restrict__ base, const uint64_t *__restrict__ offs,
-            const uint64_t *__restrict__ lens, const uint64_t *__restrict__ ids, uint64_t seed,
-            uint32_t n)
-{
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const uint64_t off = offs[i], len = lens[i];
-        if (len == 0) {
-            continue;
-        }
-        const uint64_t id = ids ? ids[i] : (uint64_t) i;
-        const uint64_t key = seed ^ (0x9E3779B97F4A7C15ull * (id + 1));
-        const uint64_t first = off & ~15ull;
-        const uint64_t ngran = ((off + len + 15) & ~15ull) - first;
-        for (uint64_t gi = threadIdx.x; gi < ngran / 16; gi += blockDim.x) {
-            const uint64_t gaddr = first + gi * 16;
-            const int64_t t0 = (int64_t) gaddr - (int64_t) off;  // chunk-relative byte of granule start
-            if (t0 >= 0 && (uint64_t) t0 + 16 <= len) {
-                const uint64_t k0 = (uint64_t) t0 >> 3;
-                const uint32_t sh = (uint32_t) (t0 & 7) * 8;
-                const uint64_t w0 = splitmix64(key + k0), w1 = splitmix64(key + k0 + 1);
-                uint64_t lo, hi;
-                if (sh == 0) {
-                    lo = w0; hi = w1;
-                } else {
-                    const uint64_t w2 = splitmix64(key + k0 + 2);
-                    lo = (w0 >> sh) | (w1 << (64 - sh));
-                    hi = (w1 >> sh) | (w2 << (64 - sh));
-                }
-                *reinterpret_cast<uint4 *>(base + gaddr) =
-                    make_uint4((uint32_t) lo, (uint32_t) (lo >> 32), (uint32_t) hi, (uint32_t) (hi >> 32));
-            } else {
-                for (int b = 0; b < 16; ++b) {
-                    const int64_t t = t0 + b;
-                    if (t >= 0 && (uint64_t) t < len) {
-                        const uint64_t w = splitmix64(key + ((uint64_t) t >> 3));
-                        base[gaddr + b] = (uint8_t) (w >> (8 * (t & 7)));
-                    }
-                }
-            }
-        }
-    }
-}
-
-#if defined(CIO_DIAG_RS_DYN)
-// Diagnostic (CIO_GPU_RS_DYN="pool_permille,U,NC"): the read-only stream with
-// a dynamic tail.  The first S - P steps are split evenly over the waves as
-// in read_stream_kernel; the last P steps form a pool of U-step units, dealt
-// over NC counters (one cache line each).  A wave that has finished its
-// static range claims units from the counter its workgroup's XCD and slot
-// hash to, moving on to the next counter when one is exhausted, so waves on
-// fast CUs take over work that slow CUs would otherwise finish late.  The
-// next unit is claimed before the current one is streamed (one returning
-// atomic in flight).  Counters are zeroed by the host before each launch.
-__global__ void __launch_bounds__(kThreads, 1)
-read_stream_dyn_kernel(const uint8_t *__restrict__ base, uint64_t S, uint64_t Sst, uint32_t U,
-                       uint32_t *__restrict__ ctr, uint32_t NC, uint32_t upc, uint32_t npool,
-                       uint32_t *__restrict__ sink)
-{
-    const uint32_t W = gridDim.x * (kThreads / kWave);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kThreads / kWave) + (threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
-    u32x4 acc = {0u, 0u, 0u, 0u};
-    auto step = [&](uint64_t g) {
-        const u32x4 *p = reinterpret_cast<const u32x4 *>(base + g * kStep + (uint64_t) lane * kGran);
-#pragma unroll
-        for (int q = 0; q < kSub; ++q) {
-            acc ^= __builtin_nontemporal_load(p + q * kWave);
-        }
-    };
-    const uint64_t g0 = wave_start(wave, Sst, W), g1 = wave_start((uint64_t) wave + 1, Sst, W);
-    for (uint64_t g = g0; g < g1; ++g) {
-        step(g);
-    }
-    // Counter c = wave mod NC: every counter is shared by waves of every XCD
-    // (so a slow XCD's share flows to the others), and a wave leaves after
-    // its own counter's first failed claim (one extra atomic per wave, no
-    // sequential tries over other counters).  Unit k of counter c covers
-    // pool steps [(k NC + c) U, +U): the counters interleave over the pool.
-    const uint32_t c = wave % NC;
-    auto claim = [&]() -> uint32_t {
-        uint32_t u = 0;
-        if (lane == 0) {
-            u = __hip_atomic_fetch_add(&ctr[c * 32u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return __builtin_amdgcn_readfirstlane(u);
-    };
-    uint32_t u = claim();
-    while (u < upc) {
-        const uint32_t unit = u * NC + c;
-        u = claim();    // the next claim in flight while this unit streams
-        if (unit < npool) {
-            const uint64_t a = Sst + (uint64_t) unit * U;
-            const uint64_t b = min(S, a + U);
-            for (uint64_t g = a; g < b; ++g) {
-                step(g);
-            }
-        }
-    }
-    const uint32_t x = wave_xor(acc[0] ^ acc[1] ^ acc[2] ^ acc[3]);
-    if (lane == 0) {
-        sink[wave] = x;
-    }
-}
-#endif  // CIO_DIAG_RS_DYN
 
 // ---------------------------------------------------------------- host side
 
@@ -1955,170 +1495,3 @@ int cioa::devplan_crc_launch(const cio_crc32_plan *p, const unsigned long long *
     HIP_TRY(hipGetLastError(), "crc32_stream_kernel (device-planned) launch");
     return CIO_OK;
 }
-
-extern "C" {
-
-int cio_gpu_fill_synthetic(void *dev_base, const uint64_t *offs, const uint64_t *lens,
-                           const uint64_t *ids, size_t n, uint64_t seed, void *stream)
-{
-    if (n == 0) {
-        return CIO_OK;
-    }
-    DeviceState *st;
-    if (device_state(&st) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    uint64_t *d_meta = nullptr;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipMalloc(&d_meta, 3 * n * sizeof(uint64_t)), "fill: hipMalloc");
-    uint64_t *d_offs = d_meta, *d_lens = d_meta + n, *d_ids = ids ? d_meta + 2 * n : nullptr;
-    hipError_t e = hipMemcpy(d_offs, offs, n * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_lens, lens, n * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && ids) e = hipMemcpy(d_ids, ids, n * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const uint32_t grid = (uint32_t) std::min<size_t>(n, 65535);
-        hipLaunchKernelGGL(fill_kernel, dim3(grid), dim3(256), 0, s,
-                           reinterpret_cast<uint8_t *>(dev_base), d_offs, d_lens, d_ids, seed,
-                           (uint32_t) n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        e = hipStreamSynchronize(s);
-    }
-    (void) hipFree(d_meta);
-    if (e != hipSuccess) {
-        return fail("fill_kernel", e);
-    }
-    return CIO_OK;
-}
-
-static unsigned long long *g_rs_stamps = nullptr;   // CIO_GPU_RS_STAMPS diagnostic
-static uint32_t g_rs_waves = 0;
-
-/* Diagnostic (not in the public header): per-wave (entry, first step, done,
- * xcc) stamps of the last CIO_GPU_RS_STAMPS=1 read-stream launch; returns the
- * number of waves. */
-int cioa_debug_rs_stamps(unsigned long long *host, size_t cap)
-{
-    if (!g_rs_stamps) {
-        return 0;
-    }
-    const size_t n = std::min(cap, (size_t) g_rs_waves * 4);
-    if (hipMemcpy(host, g_rs_stamps, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) {
-        return 0;
-    }
-    return (int) g_rs_waves;
-}
-
-static int read_stream_impl(const void *dev_base, uint64_t bytes, void *stream, hipEvent_t ev0, hipEvent_t ev1,
-                            uint32_t workgroups = 0);
-
-int cio_gpu_read_stream(const void *dev_base, uint64_t bytes, void *stream)
-{
-    return read_stream_impl(dev_base, bytes, stream, nullptr, nullptr);
-}
-
-int cio_gpu_read_stream_grid(const void *dev_base, uint64_t bytes, uint32_t workgroups, void *stream)
-{
-    if (workgroups > 65536 / (kThreads / kWave)) {
-        return fail("cio_gpu_read_stream_grid: more than 4096 workgroups");
-    }
-    return read_stream_impl(dev_base, bytes, stream, nullptr, nullptr, workgroups);
-}
-
-/* Diagnostic (not in the public header): the read-only stream with events
- * recorded right around its kernel (after the dynamic-tail counter reset). */
-int cioa_debug_read_stream_events(const void *dev_base, uint64_t bytes, void *stream, void *ev0, void *ev1)
-{
-    return read_stream_impl(dev_base, bytes, stream, reinterpret_cast<hipEvent_t>(ev0),
-                            reinterpret_cast<hipEvent_t>(ev1));
-}
-
-static int read_stream_impl(const void *dev_base, uint64_t bytes, void *stream, hipEvent_t ev0, hipEvent_t ev1,
-                            uint32_t workgroups)
-{
-    DeviceState *st;
-    if (device_state(&st) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    const uint32_t grid = workgroups ? workgroups : (uint32_t) st->cus;
-    static thread_local uint32_t *sink = nullptr;
-    if (!sink) {
-        HIP_TRY(hipMalloc(&sink, 65536 * sizeof(uint32_t)), "read_stream: hipMalloc");
-    }
-    const uint64_t S = bytes / kStep;
-    if (S == 0 || dev_base == nullptr) {
-        return CIO_OK;
-    }
-    uint32_t B = 0;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_RS_BLOCK")) {
-        B = (uint32_t) atoi(r);
-    }
-    if (const char *r = cioa_diag_getenv("CIO_GPU_RS_WGPOOL")) {
-        const int k = atoi(r);
-        if (k > 0 && k < 65536) {
-            B = 0x80000000u | (uint32_t) k;
-        }
-    }
-    unsigned long long *stamps = nullptr;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_RS_STAMPS")) {
-        if (atoi(r) > 0) {
-            if (!g_rs_stamps) {
-                HIP_TRY(hipMalloc(&g_rs_stamps, 65536 * 4 * sizeof(unsigned long long)), "read_stream: hipMalloc");
-            }
-            stamps = g_rs_stamps;
-            g_rs_waves = st->cus * (kThreads / kWave);
-        }
-    }
-    uint32_t work = 0;
-    if (const char *r = cioa_diag_getenv("CIO_GPU_RS_WORK")) {
-        work = (uint32_t) std::max(0, std::min(65535, atoi(r)));
-    }
-    if (const char *r = cioa_diag_getenv("CIO_GPU_RS_LANE")) {
-        // diagnostic: bytes per lane and step-row, 16 (coalesced rows), 32 or 64
-        const int lb = atoi(r);
-        work |= (lb == 64 ? 2u : lb == 32 ? 1u : 0u) << 16;
-    }
-#if defined(CIO_DIAG_RS_DYN)
-    if (const char *r = cioa_diag_getenv("CIO_GPU_RS_DYN")) {
-        unsigned pm = 0, U = 4, NC = 64;
-        if (sscanf(r, "%u,%u,%u", &pm, &U, &NC) >= 1 && pm > 0 && pm <= 1000 && U >= 1 && NC >= 1 &&
-            NC <= 1024) {
-            static thread_local uint32_t *ctr = nullptr;
-            if (!ctr) {
-                HIP_TRY(hipMalloc(&ctr, 1024 * 32 * sizeof(uint32_t)), "read_stream: hipMalloc");
-            }
-            const uint64_t P = S * pm / 1000;
-            const uint64_t npool = (P + U - 1) / U;
-            const uint32_t upc = (uint32_t) ((npool + NC - 1) / NC);
-            hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-            HIP_TRY(hipMemsetAsync(ctr, 0, (size_t) NC * 32 * sizeof(uint32_t), hs), "read_stream: memset");
-            if (ev0) {
-                HIP_TRY(hipEventRecord(ev0, hs), "hipEventRecord");
-            }
-            hipLaunchKernelGGL(read_stream_dyn_kernel, dim3(st->cus), dim3(kThreads), 0, hs,
-                               reinterpret_cast<const uint8_t *>(dev_base), S, S - P, (uint32_t) U, ctr,
-                               (uint32_t) NC, upc, (uint32_t) npool, sink);
-            HIP_TRY(hipGetLastError(), "read_stream_dyn_kernel launch");
-            if (ev1) {
-                HIP_TRY(hipEventRecord(ev1, hs), "hipEventRecord");
-            }
-            return CIO_OK;
-        }
-    }
-#endif
-    if (ev0) {
-        HIP_TRY(hipEventRecord(ev0, reinterpret_cast<hipStream_t>(stream)), "hipEventRecord");
-    }
-    hipLaunchKernelGGL(read_stream_kernel, dim3(grid), dim3(kThreads), 0,
-                       reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const uint8_t *>(dev_base), S, sink, B, stamps, work);
-    HIP_TRY(hipGetLastError(), "read_stream_kernel launch");
-    if (ev1) {
-        HIP_TRY(hipEventRecord(ev1, reinterpret_cast<hipStream_t>(stream)), "hipEventRecord");
-    }
-    return CIO_OK;
-}
-
-}  // extern "C"
-

@@ -1,6 +1,6 @@
 /*
  * Host copies into pinned staging (the host pipeline's copy workers,
- * crc32_gpu.hip CopyPool).  The staging image is written once and then read
+ * host_pipeline.hip CopyPool).  The staging image is written once and then read
  * by the DMA engine, never by the CPU, so its lines need not be read into the
  * cache first: 32-byte non-temporal stores skip the read-for-ownership that a
  * plain memcpy pays on every destination line, one of the three host-memory
