@@ -14,6 +14,8 @@ Layers:
                                                    init / write / seal_batch_dev;
                                                    cio_write_dev_move.h:
                                                    write_metadata / write_at_batch_dev)
+                                                   and read path (cio_read_dev.h:
+                                                   read / read_packed / meta_cmp_batch_dev)
 """
 from ._lib import LIB_PATH, CioGpuError, lib  # noqa: F401
 from .crc32 import (  # noqa: F401
@@ -25,8 +27,9 @@ from .crc32 import (  # noqa: F401
 )
 
 from .chunkfile import (  # noqa: F401,E402
-    CIOA_SEAL_RECOMPUTE, CIOA_WRITER_MOVE, DevWriter, init_batch_dev, seal_batch_dev, verify_batch_dev,
-    write_at_batch_dev, write_batch_dev, write_metadata_batch_dev,
+    CIOA_READ_CONTENT, CIOA_READ_IMAGE, CIOA_READ_META, CIOA_READ_NUL, CIOA_SEAL_RECOMPUTE, CIOA_WRITER_MOVE,
+    DevWriter, init_batch_dev, meta_cmp_batch_dev, read_batch_dev, read_packed_batch_dev, seal_batch_dev,
+    verify_batch_dev, write_at_batch_dev, write_batch_dev, write_metadata_batch_dev,
 )
 
 __version__ = "0.5.0"

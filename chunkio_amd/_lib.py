@@ -45,6 +45,8 @@ EXPORTS = (
     # include/chunkio_amd/cio_write_dev_move.h
     "cio_dev_writer_create_ex", "cio_dev_writer_move_segments", "cio_file_write_metadata_batch_dev",
     "cio_file_write_at_batch_dev",
+    # include/chunkio_amd/cio_read_dev.h
+    "cio_file_read_batch_dev", "cio_file_read_packed_batch_dev", "cio_meta_cmp_batch_dev",
     # include/chunkio_amd/cio_sync.h
     "cio_file_sync_batch", "cio_file_sync_batch_multi", "cio_file_sync_batch_begin", "cio_file_sync_batch_end",
     # include/chunkio_amd/cioa_chunk.h
@@ -113,6 +115,13 @@ def _bind(lib):
                                                              ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
         "cio_file_write_at_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V,
                                                        ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
+        "cio_file_read_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int, V,
+                                                   V, ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
+        "cio_file_read_packed_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int,
+                                                          V, V, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, V, V,
+                                                          V, V, V]),
+        "cio_meta_cmp_batch_dev": (ctypes.c_int, [V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, ctypes.c_uint64, V,
+                                                  V, V, V, V]),
         "cio_crc32_batch_host": (ctypes.c_int, [P(V), P(ctypes.c_size_t), c_u32_p, c_u32_p,
                                                 ctypes.c_size_t]),
         "cio_crc32_batch_host_multi": (ctypes.c_int, [P(V), P(ctypes.c_size_t), c_u32_p, c_u32_p,

@@ -33,6 +33,11 @@ with write_metadata_batch_dev replaces the metadata of images that already
 hold content (cio_file_write_metadata, src/cio_file.c:1075-1145: the content
 moves inside the image), and write_at_batch_dev is cio_chunk_write_at
 (src/cio_chunk.c:184-209); include/chunkio_amd/cio_write_dev_move.h.
+
+read_batch_dev / read_packed_batch_dev gather the metadata, the content or the
+trimmed image of every image of a batch into an output tensor
+(cio_meta_read, cio_file_content_copy; include/chunkio_amd/cio_read_dev.h),
+and meta_cmp_batch_dev is cio_meta_cmp.
 """
 import ctypes
 import os
@@ -53,6 +58,8 @@ CIOA_VERIFY_WRITEBACK = 64
 CIOA_SYNC_FINALIZE, CIOA_SYNC_MSYNC, CIOA_SYNC_FULL = 1, 2, 8
 CIOA_SEAL_RECOMPUTE = 256
 CIOA_WRITER_MOVE = 1
+CIOA_READ_META, CIOA_READ_CONTENT, CIOA_READ_IMAGE = 0, 1, 2
+CIOA_READ_NUL = 1
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -327,6 +334,79 @@ def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM
         int(flags), _ptr(crc_cur), _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_seal_batch_dev")
     return status[:n]
+
+
+def _u64_out(t, n, dev):
+    import torch
+    if t is None:
+        t = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    return t
+
+
+def _nbytes(t):
+    return 0 if t is None else t.numel() * t.element_size()
+
+
+def read_batch_dev(writer, base, img_offs, img_caps, what, out, out_offs=None, out_caps=None, gate=None, flags=0,
+                   out_lens=None, status=None, stream=None, out_bytes=None):
+    """Read record `what` (CIOA_READ_META / _CONTENT / _IMAGE) of image i into
+    out[out_offs[i]:+out_caps[i]] (cio_file_read_batch_dev).  out: uint8 cuda
+    tensor, or None for a size query (out_offs / out_caps are then not needed);
+    gate: int32 cuda tensor, entry i is read only when gate[i] == CIO_OK (the
+    status of a verify_batch_dev queued ahead); flags: 0 or CIOA_READ_NUL;
+    out_bytes: defaults to out's size.  The lengths are read from the images on
+    the device.  Returns (status int32, out_lens int64) cuda tensors without
+    waiting; pass `status` / `out_lens` to reuse them (under graph capture)."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    out_lens = _u64_out(out_lens, n, base.device)
+    rc = _lib.lib().cio_file_read_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, int(what), _ptr(gate),
+        _ptr(out), _nbytes(out) if out_bytes is None else int(out_bytes), _ptr(out_offs), _ptr(out_caps),
+        int(flags), _ptr(out_lens), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_read_batch_dev")
+    return status[:n], out_lens[:n]
+
+
+def read_packed_batch_dev(writer, base, img_offs, img_caps, what, out, align=1, gate=None, flags=0, out_offs=None,
+                          out_lens=None, total=None, status=None, stream=None, out_bytes=None):
+    """Read record `what` of every image into `out`, packed in index order at
+    places computed on the device (cio_file_read_packed_batch_dev): slot i is
+    the record (and its terminator with CIOA_READ_NUL) rounded up to `align`, a
+    power of two in 1..4096; a rejected entry has no slot.  out = None is a
+    size query: the placement as if `out` were unbounded.  Returns (status
+    int32, out_offs int64, out_lens int64, total int64[1]) cuda tensors without
+    waiting; total[0] is the sum of all slots whether or not it fits."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    out_offs = _u64_out(out_offs, n, base.device)
+    out_lens = _u64_out(out_lens, n, base.device)
+    if total is None:
+        total = torch.zeros(1, dtype=torch.int64, device=base.device)
+    rc = _lib.lib().cio_file_read_packed_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, int(what), _ptr(gate),
+        _ptr(out), _nbytes(out) if out_bytes is None else int(out_bytes), int(align), int(flags), _ptr(out_offs),
+        _ptr(out_lens), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_read_packed_batch_dev")
+    return status[:n], out_offs[:n], out_lens[:n], total
+
+
+def meta_cmp_batch_dev(base, img_offs, img_caps, cand, cand_offs, cand_lens, result=None, status=None, stream=None):
+    """cio_meta_cmp of image i's metadata against cand[cand_offs[i]:
+    +cand_lens[i]] (cio_meta_cmp_batch_dev).  Returns (result int32: 0 equal,
+    -1 not; status int32) cuda tensors without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    result = _status_out(result, n, base.device)
+    rc = _lib.lib().cio_meta_cmp_batch_dev(
+        _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(cand), _nbytes(cand), _ptr(cand_offs),
+        _ptr(cand_lens), _ptr(result), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_meta_cmp_batch_dev")
+    return result[:n], status[:n]
 
 
 class Context:

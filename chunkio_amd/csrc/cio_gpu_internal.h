@@ -3,7 +3,8 @@
 // crc32_gpu.hip: the CRC kernels and their launchers; probe_gpu.hip: the
 // read-only stream and the synthetic fill; devplan_gpu.hip: the device
 // planner; write_dev_gpu.hip: the write path of chunk images in HBM;
-// host_pipeline.hip: the host-memory / file batch pipeline).
+// read_dev_gpu.hip: their read path; host_pipeline.hip: the host-memory /
+// file batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
 // planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.
 #ifndef CIOA_GPU_INTERNAL_H
@@ -59,5 +60,33 @@ struct cio_crc32_devplan {
     uint64_t *roffs = nullptr, *rlens = nullptr;   // cio_file_verify_batch_dev: CRC regions
     uint32_t *rcrc = nullptr;
 };
+
+// A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
+// the write path (write_dev_gpu.hip) and of the read path (read_dev_gpu.hip).
+struct cio_dev_writer {
+    uint32_t max_chunks = 0;                 // first: the argument checks read it
+    cio_crc32_devplan *dp = nullptr;
+    uint32_t copy_grid = 0;
+    uint32_t move_grid = 0;                  // segments of the in-place move; 0 without CIOA_WRITER_MOVE
+    uint64_t *soff = nullptr, *slen = nullptr;   // validated source / CRC regions
+    uint64_t *dst = nullptr;                 // destination offsets from dev_base
+    uint32_t *newlen = nullptr;              // content length after the append
+    uint32_t *seed = nullptr;                // init: the CRC state after bytes 22..23
+    uint32_t *crc = nullptr;                 // the CRC launch's output
+    uint64_t *roff = nullptr, *rlen = nullptr;   // write_at, write_metadata: the CRC region in the image
+    uint64_t *msrc = nullptr, *mlen = nullptr;   // the move: old content (with CIOA_WRITER_MOVE)
+    int64_t *mdelta = nullptr;               // new - old metadata length
+    uint8_t *arena = nullptr;                // move_grid * kMoveSegBytes
+    uint64_t *rtot = nullptr;                // packed read: slot totals, ceil(max_chunks / kReadBlock)
+};
+
+namespace cioa {
+
+// One launch of append_copy (write_dev_gpu.hip) over the planner's image of
+// (w->soff, w->slen): record i goes from dev_src + w->soff[i] to dev_dst +
+// w->dst[i].  The read path's copy as well: source = the image buffer.
+int launch_copy(const cio_dev_writer *w, void *dev_dst, const void *dev_src, size_t n, hipStream_t s);
+
+}  // namespace cioa
 
 #endif

@@ -59,6 +59,7 @@
 #include "cio_gpu_internal.h"
 #include "write_dev_copy.h"
 #include "write_dev_move.h"
+#include "read_dev_place.h"
 #include "chunkio_amd/cio_write_dev.h"
 #include "chunkio_amd/cio_write_dev_move.h"
 
@@ -551,25 +552,9 @@ uint32_t blocks256(size_t n)
 
 }  // namespace
 
-struct cio_dev_writer {
-    uint32_t max_chunks = 0;                 // first: the argument checks read it
-    cio_crc32_devplan *dp = nullptr;
-    uint32_t copy_grid = 0;
-    uint32_t move_grid = 0;                  // segments of the in-place move; 0 without CIOA_WRITER_MOVE
-    uint64_t *soff = nullptr, *slen = nullptr;   // validated source / CRC regions
-    uint64_t *dst = nullptr;                 // destination offsets from dev_base
-    uint32_t *newlen = nullptr;              // content length after the append
-    uint32_t *seed = nullptr;                // init: the CRC state after bytes 22..23
-    uint32_t *crc = nullptr;                 // the CRC launch's output
-    uint64_t *roff = nullptr, *rlen = nullptr;   // write_at, write_metadata: the CRC region in the image
-    uint64_t *msrc = nullptr, *mlen = nullptr;   // the move: old content (with CIOA_WRITER_MOVE)
-    int64_t *mdelta = nullptr;               // new - old metadata length
-    uint8_t *arena = nullptr;                // move_grid * kMoveSegBytes
-};
+// struct cio_dev_writer: cio_gpu_internal.h (the read path shares it).
 
-namespace {
-
-int launch_copy(const cio_dev_writer *w, void *dev_base, const void *dev_src, size_t n, hipStream_t s)
+int cioa::launch_copy(const cio_dev_writer *w, void *dev_base, const void *dev_src, size_t n, hipStream_t s)
 {
     hipLaunchKernelGGL(append_copy, dim3(w->copy_grid), dim3(kCopyThreads), 0, s,
                        reinterpret_cast<uint8_t *>(dev_base), reinterpret_cast<const uint8_t *>(dev_src),
@@ -577,6 +562,8 @@ int launch_copy(const cio_dev_writer *w, void *dev_base, const void *dev_src, si
     HIP_TRY(hipGetLastError(), "append_copy launch");
     return CIO_OK;
 }
+
+namespace {
 
 // The argument checks every entry point shares, before any device call.
 // Returns 1 when the call is a no-op (n == 0), 0 to go on, CIO_ERROR.
@@ -655,6 +642,7 @@ void cio_dev_writer_destroy(cio_dev_writer *w)
     (void) hipFree(w->mlen);
     (void) hipFree(w->mdelta);
     (void) hipFree(w->arena);
+    (void) hipFree(w->rtot);
     delete w;
 }
 
@@ -699,7 +687,8 @@ int cio_dev_writer_create_ex(cio_dev_writer **out, size_t max_chunks, int flags)
         (e = hipMalloc(&w->seed, max_chunks * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc(&w->crc, max_chunks * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc(&w->roff, max_chunks * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipMalloc(&w->rlen, max_chunks * sizeof(uint64_t))) != hipSuccess) {
+        (e = hipMalloc(&w->rlen, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->rtot, ((max_chunks + kReadBlock - 1) / kReadBlock) * sizeof(uint64_t))) != hipSuccess) {
         cio_dev_writer_destroy(w);
         return fail("cio_dev_writer_create: device allocation", e);
     }
