@@ -106,6 +106,12 @@ class Crc32Plan:
         """The kernel this plan launches (crc32_stream_kernel / crc32_small_kernel)."""
         return _lib.lib().cio_crc32_plan_kernel(self._handle).decode()
 
+    @property
+    def aligned(self):
+        """True for a wave-aligned plan (cio_crc32_plan_aligned): the stream
+        kernel's compile-time path."""
+        return bool(_lib.lib().cio_crc32_plan_aligned(self._handle))
+
     def exec(self, base, out, seeds=None, stream=None):
         """base: uint8 cuda tensor; out: int32/uint32 cuda tensor of n; seeds: same or None."""
         _lib.check(_lib.lib().cio_crc32_plan_exec(self._handle, _ptr(base), _ptr(seeds), _ptr(out),

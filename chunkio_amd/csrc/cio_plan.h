@@ -73,6 +73,7 @@ struct PlanHost {
     std::vector<WaveStart> ws;
     std::vector<uint32_t> tiny;
     std::vector<uint32_t> pfac;   // per piece slot (wave + chunk), then W wave flags, then W last-piece factors
+    std::vector<uint32_t> afac;   // wave-aligned plans only: [piece][lane] fold factors (plan_choose)
     uint64_t S = 0, bytes = 0;
 };
 
@@ -113,6 +114,12 @@ struct cio_crc32_plan {
     bool ahead = false;        // uniform, 16-B aligned, whole 4 KiB steps: issue-ahead stream kernel
     bool l64 = false;          // stream kernels: one 64-byte chain per lane (CIO_GPU_L64)
     bool l64_small = false;    // the same layout in the small-chunk kernel
+    // Wave-aligned uniform batch (plan_choose): every wave owns exactly aq
+    // steps and every chunk is 1 << alg2p consecutive waves of one workgroup;
+    // crc32_aligned_kernel reads no plan array but afac.
+    bool aligned = false;
+    uint32_t aq = 0, alg2p = 0;
+    uint32_t *afac = nullptr;  // device copy of PlanHost::afac
     unsigned long long *stamps = nullptr;   // CIO_GPU_STAMPS=1: diagnostic timestamps
     uint64_t bytes = 0;        // sum of lens
     cioa::ChunkDesc *desc = nullptr;

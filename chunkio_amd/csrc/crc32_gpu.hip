@@ -1126,6 +1126,240 @@ crc32_stream_kernel(const uint8_t *base, uint64_t S_arg, uint64_t ustride, uint6
     }
 }
 
+// ---------------------------------------------------------------- wave-aligned
+
+// The stream kernel for wave-aligned plans (plan_choose, cio_plan.h): a
+// uniform batch of whole 4 KiB steps without alignment head in which every
+// wave owns exactly q steps and every chunk is exactly p = 1 << lgp
+// consecutive waves of one workgroup (cfg2: q = 25, p = 4).  Wave w then holds
+// piece w mod p of chunk w / p, its only piece end is its last step, and
+// nothing is shared between workgroups: the kernel reads no descriptor, no
+// wave record, no per-wave plan word, no partial slot and no arrival counter.
+// Everything the first data request needs arrives in preloaded arguments.
+// Same lanes (L64), tables, issue-ahead ring and priority rotation as
+// crc32_stream_kernel<.., UNIFORM, AHEAD, L64>; what is gone is
+//   start-up: the split arithmetic (two 64-bit split points and a chunk index
+//     per wave on the CU's one scalar unit), the kernel-argument loads and the
+//     per-lane descriptor / g_x8 / per-wave-word loads behind them;
+//   every step: the piece-end test, the chunk advance, the j == 0 head test
+//     and the second iteration's multiply of the last-piece factor (afac holds
+//     the product per piece and lane, computed by the host);
+//   tail: the drain of partial stores, the arrival scan and tiny_chunks; the
+//     one multiply by the fold factor is 32 independent masked XORs.
+// rotate_prio's run-time choice of the level stays: a main loop of four steps
+// with the level a constant at each position, specialised by slot group,
+// measured the same (profiles/r11/ab_ladder_vs_unroll4.txt).
+// afac: [p][64] factors x^(8 (4096 q (p - 1 - i) + 64 (63 - l))), which shift
+// lane l's state at the end of piece i to the chunk end.
+template <bool STAMPS = false>
+__global__ void __launch_bounds__(kThreads, 1)
+crc32_aligned_kernel(const uint8_t *base, uint64_t ustride, uint64_t ua0, uint32_t q, uint32_t lgp,
+                     const uint32_t *__restrict__ afac, const uint32_t *__restrict__ seeds, uint32_t *out,
+                     const uint32_t *__restrict__ cid, unsigned long long *stamps)
+{
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
+    const uint32_t tid = threadIdx.x;
+    unsigned long long t_entry = 0, t_tables = 0, t_stream = 0, t_first = 0, t_mid = 0, t_issued = 0;
+    unsigned long long t_wt[2] = {0, 0}, t_step1 = 0, t_bar1 = 0, t_bar2 = 0, t_folded = 0;
+    if (STAMPS) {
+        t_entry = __builtin_amdgcn_s_memrealtime();
+    }
+    const uint32_t wslot = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave of the workgroup
+    const uint32_t wave = blockIdx.x * (uint32_t) kWavesPerWg + wslot;
+    const uint32_t lane = tid & 63u;
+    const uint32_t np = 1u << lgp;
+    const uint32_t c = wave >> lgp, piece = wave & (np - 1u);
+    // (piece * q * kStep < 16 * 64 * 4096)
+    const uint8_t *cbase = base + (ua0 + (uint64_t) c * ustride + (uint64_t) (piece * q * (uint32_t) kStep));
+
+    StepRegs cur, nxt;
+    load_step64(cur, cbase, 0, lane);
+    // The data requests leave first; the one bookkeeping load, this lane's
+    // fold factor, follows them (afac is a preloaded argument).
+    __builtin_amdgcn_sched_barrier(0);
+    const uint32_t fac = afac[piece * (uint32_t) kWave + lane];
+    __builtin_amdgcn_sched_barrier(0);
+    if (STAMPS) {
+        t_issued = __builtin_amdgcn_s_memrealtime();
+    }
+    const uint32_t lb_lo = (lane & kSliceRepMask) << 2;
+    const uint32_t lb_hi = lb_lo | 0x10000u;
+    const uint32_t lrep = (lane & kShiftRepMask) << 2;
+    const uint32_t slot_group = wslot >> 2;
+    {
+        uint32_t tab_v[kE], tab_sv[kE];
+        table_entries<cx_xpow8n(kStep - 64)>(__builtin_amdgcn_readfirstlane(tid >> 8), tid & 255u, tab_v[0],
+                                             tab_sv[0]);
+        write_tables<STAMPS>(lds, tid, tab_v, tab_sv, t_wt);
+    }
+    __syncthreads();
+    if (STAMPS) {
+        t_tables = __builtin_amdgcn_s_memrealtime();
+    }
+
+    // The chunk's output (and seed) index; the seed goes into the first
+    // piece's content bytes 0..3: register 0 of lane 0, which the transpose
+    // leaves in place.
+    const bool first_piece = piece == 0, final_piece = piece == np - 1u;
+    uint32_t oc = c;
+    if (cid && (first_piece || final_piece)) {
+        oc = cid[c];
+    }
+    uint32_t seed = 0;
+    if (first_piece) {
+        seed = seeds ? seeds[oc] : 0xffffffffu;
+    }
+    auto landed = [](StepRegs &r) {
+        asm volatile("" : "+v"(r.q[0].x), "+v"(r.q[0].y), "+v"(r.q[0].z), "+v"(r.q[0].w),
+                          "+v"(r.q[1].x), "+v"(r.q[1].y), "+v"(r.q[1].z), "+v"(r.q[1].w),
+                          "+v"(r.q[2].x), "+v"(r.q[2].y), "+v"(r.q[2].z), "+v"(r.q[2].w),
+                          "+v"(r.q[3].x), "+v"(r.q[3].y), "+v"(r.q[3].z), "+v"(r.q[3].w));
+    };
+    landed(cur);
+    cur.q[0].x ^= lane == 0 ? seed : 0u;
+    if (STAMPS) {
+        t_first = __builtin_amdgcn_s_memrealtime();
+    }
+
+    // The ring of crc32_stream_kernel's AHEAD path: two fixed register slots,
+    // the other slot's refill issued once this slot's data has landed and
+    // before its CRC; the wave's last step is peeled and refills nothing.
+    uint32_t s0 = 0;
+    // The multiply by the lane's fold factor at the piece end as a 32 x 32
+    // GF(2) matrix held in registers (column j = fac * x^(31 - j), as in
+    // crc32_small_kernel): 32 independent masked XORs at the wave's end, where
+    // its latency counts, instead of multmodp's 32 dependent rounds.  Built in
+    // the wave's first step behind the second step's requests (`first`), off
+    // the start-up path; the asm pins it there.
+    uint32_t col[32];
+    auto half = [&](uint32_t it, StepRegs &use, StepRegs &fill, auto refill, auto first) {
+        rotate_prio(slot_group, it);
+        landed(use);
+        if (decltype(refill)::value) {
+            load_step64(fill, cbase, it + 1, lane);
+        }
+        if (decltype(first)::value) {
+            col[31] = fac;
+#pragma unroll
+            for (int j = 30; j >= 0; --j) {
+                col[j] = (col[j + 1] >> 1) ^ (CIOA_POLY & (0u - (col[j + 1] & 1u)));
+            }
+#pragma unroll
+            for (int j = 0; j < 32; j += 8) {
+                asm volatile("" : "+v"(col[j]), "+v"(col[j + 1]), "+v"(col[j + 2]), "+v"(col[j + 3]),
+                                  "+v"(col[j + 4]), "+v"(col[j + 5]), "+v"(col[j + 6]), "+v"(col[j + 7]));
+            }
+        }
+        // one chain per lane: jump 4032 bytes, then 64 contiguous bytes
+        const uint32_t h0 = step_shift(lds, lrep, s0);
+        transpose64(use);
+        uint32_t st = block16(lds, lb_lo, lb_hi, h0, use.q[0]);
+#pragma unroll
+        for (int k = 1; k < kSub; ++k) {
+            st = block16(lds, lb_lo, lb_hi, st, use.q[k]);
+        }
+        s0 = st;
+        if (STAMPS && it == 0) {
+            t_step1 = __builtin_amdgcn_s_memrealtime();
+        }
+        if (STAMPS && it == q / 2) {
+            t_mid = __builtin_amdgcn_s_memrealtime();
+        }
+    };
+    using Refill = std::true_type;
+    using NoRefill = std::false_type;
+    using First = std::true_type;
+    using Later = std::false_type;
+    if (q == 1) {
+        half(0, cur, nxt, NoRefill(), First());
+    } else {
+        // The first step is peeled (it builds col), so the loop starts on slot nxt.
+        half(0, cur, nxt, Refill(), First());
+        uint32_t it = 1;
+        for (; it + 2 < q; it += 2) {
+            half(it, nxt, cur, Refill(), Later());
+            half(it + 1, cur, nxt, Refill(), Later());
+        }
+        if (q - it == 2) {
+            half(it, nxt, cur, Refill(), Later());
+            half(it + 1, cur, nxt, NoRefill(), Later());
+        } else {
+            half(it, nxt, cur, NoRefill(), Later());
+        }
+    }
+    __builtin_amdgcn_s_setprio(0);
+    if (STAMPS) {
+        t_stream = __builtin_amdgcn_s_memrealtime();
+    }
+
+    // The piece end, once: shift the lane's state to the chunk end (s0 * fac,
+    // one bit-field sign extend and one fused and-xor per bit, four
+    // accumulators) and reduce over the wave.
+    uint32_t acc[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        acc[j & 3] = xor_and(acc[j & 3], 0u - ((s0 >> j) & 1u), col[j]);
+    }
+    const uint32_t contrib = wave_xor(xor3(acc[0], acc[1], acc[2]) ^ acc[3]);
+
+    // Hand-over of the p - 1 earlier pieces to the wave holding the final one,
+    // through one LDS word per wave.  The tables fill all of the CU's LDS and
+    // other waves look entries up until their own last step, so the words can
+    // only be stored after a barrier that every wave passes behind its last
+    // lookup, and only be read after a second one: two barriers, as in
+    // crc32_stream_kernel, with nothing else between the stream and the fold.
+    __syncthreads();
+    if (STAMPS) {
+        t_bar1 = __builtin_amdgcn_s_memrealtime();
+    }
+    uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
+    if (!final_piece && lane == 0) {
+        slot[wslot] = contrib;
+    }
+    __syncthreads();
+    if (STAMPS) {
+        t_bar2 = __builtin_amdgcn_s_memrealtime();
+    }
+    if (final_piece) {
+        // Lane i < p - 1 <-> piece i of this chunk, wave wslot - (p - 1) + i.
+        uint32_t x = 0;
+        if (lane < np - 1u) {
+            x = slot[wslot - (np - 1u) + lane];
+        }
+        x = wave_xor(x) ^ contrib;
+        if (lane == 0) {
+            out[oc] = x;
+        }
+    }
+    if (STAMPS) {
+        t_folded = __builtin_amdgcn_s_memrealtime();
+    }
+    if (STAMPS && lane == 0) {
+        // The stamp points of crc32_stream_kernel (tools/stamps.py); there is
+        // no arrival step, so its stamp is the stream's end.
+        uint32_t hw_id, xcc_id;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
+        unsigned long long *ws = stamps + (size_t) kStampWords * wave;
+        ws[0] = t_entry;
+        ws[1] = t_tables;
+        ws[2] = t_stream;
+        ws[3] = __builtin_amdgcn_s_memrealtime();
+        ws[4] = hw_id;
+        ws[5] = xcc_id;
+        ws[6] = t_first;
+        ws[7] = t_mid;
+        ws[8] = t_issued;
+        ws[9] = t_wt[0];
+        ws[10] = t_wt[1];
+        ws[11] = t_step1;
+        ws[12] = t_stream;
+        ws[13] = t_bar1;
+        ws[14] = t_bar2;
+        ws[15] = t_folded;
+    }
+}
+
 // ---------------------------------------------------------------- small chunks
 
 // Batches whose chunks all fit one wave-step (virtual length <= 4096 B, e.g.
@@ -1387,6 +1621,15 @@ int cioa_debug_stamps(const cio_crc32_plan *p, unsigned long long *host, size_t 
     return (int) p->W;
 }
 
+/* Test hook (not in the public header): cio_crc32_plan_exec with a chunk-id
+ * map, as the host pipeline launches its groups: chunk i's seed is
+ * dev_seeds[dev_cid[i]] and its CRC goes to dev_out[dev_cid[i]]. */
+int cioa_debug_plan_exec_cid(const cio_crc32_plan *p, const void *dev_base, const uint32_t *dev_seeds,
+                             uint32_t *dev_out, const uint32_t *dev_cid, void *stream)
+{
+    return plan_exec_impl(p, dev_base, dev_seeds, dev_out, dev_cid, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
 
 using StreamKernel = decltype(&crc32_stream_kernel<false, 1, false>);
@@ -1454,6 +1697,17 @@ int cioa::plan_exec_impl(const cio_crc32_plan *p, const void *dev_base, const ui
                            reinterpret_cast<const uint8_t *>(dev_base), p->ustride, p->ua0, p->uvlen, p->uh,
                            p->W, p->n, p->ntiny, st->x8, p->desc, p->tiny, dev_seeds, dev_out, st->xinv8);
         HIP_TRY(hipGetLastError(), "crc32_small_kernel launch");
+        if (ev1) {
+            HIP_TRY(hipEventRecord(ev1, s), "hipEventRecord");
+        }
+        return CIO_OK;
+    }
+    if (p->aligned) {
+        // Wave-aligned plan: the geometry is in the arguments, afac is the only array.
+        auto ak = p->stamps ? crc32_aligned_kernel<true> : crc32_aligned_kernel<false>;
+        hipLaunchKernelGGL(ak, dim3(p->grid), dim3(kThreads), 0, s, reinterpret_cast<const uint8_t *>(dev_base),
+                           p->ustride, p->ua0, p->aq, p->alg2p, p->afac, dev_seeds, dev_out, cid, p->stamps);
+        HIP_TRY(hipGetLastError(), "crc32_aligned_kernel launch");
         if (ev1) {
             HIP_TRY(hipEventRecord(ev1, s), "hipEventRecord");
         }

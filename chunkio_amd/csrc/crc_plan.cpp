@@ -279,6 +279,42 @@ const char *plan_choose(cio_crc32_plan *p, PlanHost &ph, const uint64_t *offs, c
     }
     p->ahead = p->ahead && short_ranges;
 
+    // Wave-aligned batch: an issue-ahead batch on the full one-workgroup-per-CU
+    // grid whose S steps split into exactly q per wave, with every chunk
+    // exactly p = 2, 4, 8 or 16 consecutive waves (cfg2: q = 25, p = 4).  p
+    // divides the 16 waves of a workgroup, so wave w holds piece w mod p of
+    // chunk w / p, no chunk leaves its workgroup and a wave's only piece end
+    // is its last step: crc32_aligned_kernel derives all of it from the
+    // kernel arguments.  (p = 1, whole chunks per wave, stays on the issue-
+    // ahead kernel, which writes such chunks out directly.)
+    // CIO_GPU_ALIGNED=0 keeps the issue-ahead kernel.
+    p->aligned = false;
+    ph.afac.clear();
+    {
+        const char *r = cioa_diag_getenv("CIO_GPU_ALIGNED");
+        const bool on = !(r && atoi(r) == 0);
+        const uint64_t q = p->W ? p->S / p->W : 0;
+        if (on && p->ahead && p->l64 && p->prio && p->ntiny == 0 && p->grid == (uint32_t) p->st->cus &&
+            q >= 1 && q <= 64 && p->S == q * p->W && p->unsteps % q == 0) {
+            const uint64_t np = p->unsteps / q;
+            if (np == 2 || np == 4 || np == 8 || np == 16) {
+                p->aligned = true;
+                p->aq = (uint32_t) q;
+                p->alg2p = np == 2 ? 1 : np == 4 ? 2 : np == 8 ? 3 : 4;
+                // Piece i of a chunk ends q * 4096 * (p - 1 - i) bytes before
+                // the chunk end, and lane l's 64-byte chain 64 (63 - l) bytes
+                // before the piece end: one factor per (piece, lane) shifts a
+                // lane's state to the chunk end.
+                ph.afac.resize(np * kWave);
+                for (uint64_t i = 0; i < np; i++) {
+                    for (uint64_t l = 0; l < (uint64_t) kWave; l++) {
+                        ph.afac[i * kWave + l] = cioa_xpow8n(q * kStep * (np - 1 - i) + 64 * (kWave - 1 - l));
+                    }
+                }
+            }
+        }
+    }
+
     // The small-chunk kernel for a small-chunk batch (CIO_GPU_SMALL=0 disables).
     p->small = small_batch();
     if (const char *r = cioa_diag_getenv("CIO_GPU_SMALL")) {
@@ -360,6 +396,29 @@ int cioa_debug_plan_choice(const uint64_t *offs, const uint64_t *lens, size_t n,
     const uint32_t words[11] = {p.grid, p.W, p.small, p.ahead, p.unsteps, p.l64, p.l64_small,
                                 (uint32_t) p.S, (uint32_t) (p.S >> 32), (uint32_t) ntiny, (uint32_t) (ntiny >> 32)};
     memcpy(out_words, words, sizeof(words));
+    return 0;
+}
+
+/* Test hook (not in the public header; host only, no device): the wave-aligned
+ * class of the same choice (cio_crc32_plan_aligned on a device).  out_words[3]:
+ * aligned, steps per wave q, waves per chunk p (both 0 outside the class).
+ * Returns 0, or -1 on a plan error. */
+int cioa_debug_plan_aligned(const uint64_t *offs, const uint64_t *lens, size_t n, int cus, uint32_t *out_words)
+{
+    if (cus < 1 || n >= 0xffffffffull) {
+        return -1;
+    }
+    DeviceState st;
+    st.cus = cus;
+    cio_crc32_plan p;
+    PlanHost ph;
+    plan_init(&p, &st, n);
+    if (plan_choose(&p, ph, offs, lens, n) != nullptr) {
+        return -1;
+    }
+    out_words[0] = p.aligned;
+    out_words[1] = p.aligned ? p.aq : 0;
+    out_words[2] = p.aligned ? 1u << p.alg2p : 0;
     return 0;
 }
 

@@ -118,7 +118,7 @@ const char *cio_gpu_version(void)
 {
 #define CIO_STR2(x) #x
 #define CIO_STR(x) CIO_STR2(x)
-    return "chunkio_amd crc32 v9 gfx950 stream(l64-lanes permlane-transpose issue-ahead<=64steps pre-shift prio-rotate "
+    return "chunkio_amd crc32 v9 gfx950 stream(l64-lanes permlane-transpose issue-ahead<=64steps wave-aligned pre-shift prio-rotate "
            "coalesced-nt division-free-start slice4-lds32x perm direct-whole preshifted-partials wg-lds-fold "
            "head-align=" CIO_STR(CIO_HEAD_ALIGN) ") "
            "small(4x16B dpp-reduce bitop3-fold prio-rotate) "
@@ -143,6 +143,7 @@ void cio_crc32_plan_destroy(cio_crc32_plan *p)
     (void) hipFree(p->partials);
     (void) hipFree(p->counters);
     (void) hipFree(p->pfac);
+    (void) hipFree(p->afac);
     (void) hipFree(p->stamps);
     delete p;
 }
@@ -187,7 +188,11 @@ int cio_crc32_plan_create(cio_crc32_plan **out, const uint64_t *offs, const uint
         (ph.tiny.size() && (e = hipMemcpy(p->tiny, ph.tiny.data(), ph.tiny.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) ||
         (e = hipMemset(p->partials, 0, npart * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipMemset(p->counters, 0, std::max<size_t>(1, n) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemcpy(p->pfac, ph.pfac.data(), npart * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) {
+        (e = hipMemcpy(p->pfac, ph.pfac.data(), npart * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess ||
+        // (a wave-aligned plan launches with afac alone; the other arrays stay, unused)
+        (p->aligned && ((e = hipMalloc(&p->afac, ph.afac.size() * sizeof(uint32_t))) != hipSuccess ||
+                        (e = hipMemcpy(p->afac, ph.afac.data(), ph.afac.size() * sizeof(uint32_t),
+                                       hipMemcpyHostToDevice)) != hipSuccess))) {
         cio_crc32_plan_destroy(p);
         return fail("cio_crc32_plan_create: device allocation/upload", e);
     }
@@ -208,6 +213,11 @@ uint32_t cio_crc32_plan_workgroups(const cio_crc32_plan *p)
 const char *cio_crc32_plan_kernel(const cio_crc32_plan *p)
 {
     return (p && p->small) ? "crc32_small_kernel" : "crc32_stream_kernel";
+}
+
+int cio_crc32_plan_aligned(const cio_crc32_plan *p)
+{
+    return (p && p->aligned) ? 1 : 0;
 }
 
 int cio_crc32_plan_exec_events(const cio_crc32_plan *p, const void *dev_base,

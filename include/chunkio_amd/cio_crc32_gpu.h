@@ -135,6 +135,13 @@ uint64_t cio_crc32_plan_bytes(const cio_crc32_plan *plan);
  * batches) or "crc32_small_kernel" (every chunk within one 4 KiB wave-step). */
 const char *cio_crc32_plan_kernel(const cio_crc32_plan *plan);
 
+/* 1 when the plan is in the wave-aligned class of "crc32_stream_kernel" plans
+ * (a uniform batch of whole 4 KiB steps on the one-workgroup-per-CU grid in
+ * which every wave owns the same number of steps and every chunk is 2, 4, 8 or
+ * 16 consecutive waves of one workgroup: it runs the kernel's compile-time
+ * path, which reads no plan array), else 0. */
+int cio_crc32_plan_aligned(const cio_crc32_plan *plan);
+
 /* ---- several device-resident batches in flight ---------------------------
  *
  * A ring of `depth` (1..8) plans of one geometry, each with its own stream.

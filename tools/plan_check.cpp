@@ -51,7 +51,8 @@ std::vector<uint64_t> cfg3_lens()
 }
 
 // One geometry on a device of `cus` compute units; want_grid 0: any.
-void check(const char *name, const std::vector<uint64_t> &lens, uint64_t align, int cus, uint32_t want_grid)
+void check(const char *name, const std::vector<uint64_t> &lens, uint64_t align, int cus, uint32_t want_grid,
+           int want_aligned = -1)
 {
     const std::vector<uint64_t> offs = packed(lens, align);
     const size_t n = lens.size();
@@ -82,10 +83,13 @@ void check(const char *name, const std::vector<uint64_t> &lens, uint64_t align, 
         pieces += ph.desc[k].nsteps ? ph.desc[k].npieces : 0;
     }
     const bool ok = pairs == pieces && (want_grid == 0 || p.grid == want_grid) && p.W == p.grid * kWavesPerWg &&
-                    p.S == ph.S && p.ntiny == ph.tiny.size() && ph.ws.size() == p.W;
-    printf("%s %s: cus %d grid %u small %d ahead %d S %llu pieces %llu pairs %llu\n", ok ? "ok  " : "FAIL", name,
-           cus, p.grid, (int) p.small, (int) p.ahead, (unsigned long long) p.S, (unsigned long long) pieces,
-           (unsigned long long) pairs);
+                    p.S == ph.S && p.ntiny == ph.tiny.size() && ph.ws.size() == p.W &&
+                    (want_aligned < 0 || (int) p.aligned == want_aligned) &&
+                    ph.afac.size() == (p.aligned ? (size_t) kWave << p.alg2p : 0) &&
+                    (!p.aligned || ((uint64_t) p.aq * p.W == p.S && ((uint64_t) p.aq << p.alg2p) == p.unsteps));
+    printf("%s %s: cus %d grid %u small %d ahead %d aligned %d S %llu pieces %llu pairs %llu\n", ok ? "ok  " : "FAIL",
+           name, cus, p.grid, (int) p.small, (int) p.ahead, (int) p.aligned, (unsigned long long) p.S,
+           (unsigned long long) pieces, (unsigned long long) pairs);
     g_failed |= !ok;
 }
 
@@ -95,8 +99,14 @@ int main()
 {
     const int cus = 256;
     check("cfg3 packed", cfg3_lens(), 1, cus, 4 * cus);
-    check("cfg2 align 16", std::vector<uint64_t>(1024, 409600), 16, cus, cus);
-    check("1024 x 4 MiB", std::vector<uint64_t>(1024, 4 << 20), 1, cus, cus);
+    check("cfg2 align 16", std::vector<uint64_t>(1024, 409600), 16, cus, cus, 1);
+    // the wave-aligned class and its neighbours (tests/test_plan_aligned.py)
+    check("aligned 256 x 16 x 3 steps", std::vector<uint64_t>(256, 48 * 4096), 16, cus, cus, 1);
+    check("aligned 2048 x 2 x 1 step", std::vector<uint64_t>(2048, 2 * 4096), 16, cus, cus, 1);
+    check("not aligned: one chunk more", std::vector<uint64_t>(2049, 2 * 4096), 16, cus, cus, 0);
+    check("not aligned: whole chunks per wave", std::vector<uint64_t>(4096, 5 * 4096), 16, cus, cus, 0);
+    check("not aligned: 32 waves per chunk", std::vector<uint64_t>(128, 32 * 3 * 4096), 16, cus, cus, 0);
+    check("1024 x 4 MiB", std::vector<uint64_t>(1024, 4 << 20), 1, cus, cus, 0);
     check("8192 x 4 MiB", std::vector<uint64_t>(8192, 4 << 20), 1, cus, 4 * cus);
     check("4096 x 4096 B", std::vector<uint64_t>(4096, 4096), 1, cus, 0);
     check("empty", std::vector<uint64_t>(), 1, cus, cus);
