@@ -45,6 +45,8 @@ EXPORTS = (
     # include/chunkio_amd/cio_write_dev_move.h
     "cio_dev_writer_create_ex", "cio_dev_writer_move_segments", "cio_file_write_metadata_batch_dev",
     "cio_file_write_at_batch_dev",
+    # include/chunkio_amd/cio_write_dev_records.h
+    "cio_file_write_records_batch_dev",
     # include/chunkio_amd/cio_read_dev.h
     "cio_file_read_batch_dev", "cio_file_read_packed_batch_dev", "cio_meta_cmp_batch_dev",
     # include/chunkio_amd/cio_sync.h
@@ -116,6 +118,9 @@ def _bind(lib):
                                                              ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
         "cio_file_write_at_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V,
                                                        ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
+        "cio_file_write_records_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V,
+                                                            ctypes.c_uint64, V, V, V, ctypes.c_size_t, ctypes.c_int,
+                                                            V, V, V, V]),
         "cio_file_read_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int, V,
                                                    V, ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
         "cio_file_read_packed_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int,

@@ -34,6 +34,10 @@ hold content (cio_file_write_metadata, src/cio_file.c:1075-1145: the content
 moves inside the image), and write_at_batch_dev is cio_chunk_write_at
 (src/cio_chunk.c:184-209); include/chunkio_amd/cio_write_dev_move.h.
 
+write_records_batch_dev is the grouped append: many records per image in one
+call, the records grouped by image
+(include/chunkio_amd/cio_write_dev_records.h).
+
 read_batch_dev / read_packed_batch_dev gather the metadata, the content or the
 trimmed image of every image of a batch into an output tensor
 (cio_meta_read, cio_file_content_copy; include/chunkio_amd/cio_read_dev.h),
@@ -320,6 +324,31 @@ def write_at_batch_dev(writer, base, img_offs, img_caps, at_offs, src, src_offs,
         _ptr(crc_cur), _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_write_at_batch_dev")
     return status[:n]
+
+
+def write_records_batch_dev(writer, base, img_offs, img_caps, src, rec_img, rec_offs, rec_lens, crc_cur,
+                            flags=CIO_CHECKSUM, img_status=None, rec_status=None, stream=None):
+    """Append record r, src[rec_offs[r]:+rec_lens[r]], to image rec_img[r]
+    (cio_file_write_records_batch_dev): many records per image in one call.
+    rec_img (int32 cuda tensor holding uint32 indices) must be non-decreasing:
+    the records of an image form one run and are appended in that order; a
+    malformed grouping rejects the whole batch.  The accepted records of a run
+    are exactly those before the first rejected one.  crc_cur (int32 cuda
+    tensor of n_img) is updated in place when flags has CIO_CHECKSUM.  Returns
+    (img_status, rec_status) int32 cuda tensors without waiting; pass them in
+    to reuse them (under graph capture)."""
+    from .crc32 import _ptr, _stream_ptr
+    n_img, n_rec = int(img_offs.numel()), int(rec_img.numel())
+    if rec_img.element_size() != 4:
+        raise ValueError("rec_img must be a 32-bit tensor")
+    img_status = _status_out(img_status, n_img, base.device)
+    rec_status = _status_out(rec_status, n_rec, base.device)
+    rc = _lib.lib().cio_file_write_records_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n_img,
+        _ptr(src), src.numel() * src.element_size(), _ptr(rec_img), _ptr(rec_offs), _ptr(rec_lens), n_rec,
+        int(flags), _ptr(crc_cur), _ptr(img_status), _ptr(rec_status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_write_records_batch_dev")
+    return img_status[:n_img], rec_status[:n_rec]
 
 
 def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM, status=None, stream=None):

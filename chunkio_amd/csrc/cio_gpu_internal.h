@@ -3,7 +3,8 @@
 // crc32_gpu.hip: the CRC kernels and their launchers; probe_gpu.hip: the
 // read-only stream and the synthetic fill; devplan_gpu.hip: the device
 // planner; write_dev_gpu.hip: the write path of chunk images in HBM;
-// read_dev_gpu.hip: their read path; host_pipeline.hip: the host-memory /
+// read_dev_gpu.hip: their read path; write_records_gpu.hip: the grouped
+// append; host_pipeline.hip: the host-memory /
 // file batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
 // planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.
@@ -62,7 +63,8 @@ struct cio_crc32_devplan {
 };
 
 // A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
-// the write path (write_dev_gpu.hip) and of the read path (read_dev_gpu.hip).
+// the write path (write_dev_gpu.hip, write_records_gpu.hip) and of the read
+// path (read_dev_gpu.hip).
 struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
     cio_crc32_devplan *dp = nullptr;
@@ -78,6 +80,10 @@ struct cio_dev_writer {
     int64_t *mdelta = nullptr;               // new - old metadata length
     uint8_t *arena = nullptr;                // move_grid * kMoveSegBytes
     uint64_t *rtot = nullptr;                // packed read: slot totals, ceil(max_chunks / kReadBlock)
+    uint64_t *groom = nullptr;               // grouped append: room per image
+    uint64_t *gsum = nullptr;                // its scan's workgroup aggregates, ceil(max_chunks / kRecBlock)
+    uint32_t *gflag = nullptr;
+    uint32_t *ghdr = nullptr;                // one word: the batch's grouping is malformed
 };
 
 namespace cioa {

@@ -60,6 +60,7 @@
 #include "write_dev_copy.h"
 #include "write_dev_move.h"
 #include "read_dev_place.h"
+#include "write_dev_records.h"
 #include "chunkio_amd/cio_write_dev.h"
 #include "chunkio_amd/cio_write_dev_move.h"
 
@@ -643,6 +644,10 @@ void cio_dev_writer_destroy(cio_dev_writer *w)
     (void) hipFree(w->mdelta);
     (void) hipFree(w->arena);
     (void) hipFree(w->rtot);
+    (void) hipFree(w->groom);
+    (void) hipFree(w->gsum);
+    (void) hipFree(w->gflag);
+    (void) hipFree(w->ghdr);
     delete w;
 }
 
@@ -688,7 +693,11 @@ int cio_dev_writer_create_ex(cio_dev_writer **out, size_t max_chunks, int flags)
         (e = hipMalloc(&w->crc, max_chunks * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc(&w->roff, max_chunks * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMalloc(&w->rlen, max_chunks * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipMalloc(&w->rtot, ((max_chunks + kReadBlock - 1) / kReadBlock) * sizeof(uint64_t))) != hipSuccess) {
+        (e = hipMalloc(&w->rtot, ((max_chunks + kReadBlock - 1) / kReadBlock) * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->groom, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->gsum, ((max_chunks + kRecBlock - 1) / kRecBlock) * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->gflag, ((max_chunks + kRecBlock - 1) / kRecBlock) * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->ghdr, 2 * sizeof(uint32_t))) != hipSuccess) {
         cio_dev_writer_destroy(w);
         return fail("cio_dev_writer_create: device allocation", e);
     }

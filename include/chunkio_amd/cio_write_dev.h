@@ -53,7 +53,9 @@
  *
  * Metadata written or replaced AFTER content moves the content inside the
  * image (cio_file_write_metadata, src/cio_file.c:1075-1145), and write_at cuts
- * it: both are in cio_write_dev_move.h, which extends this header.  Growing an
+ * it: both are in cio_write_dev_move.h, which extends this header.  Appending
+ * MANY records to an image in one call (these calls take at most one per
+ * image) is in cio_write_dev_records.h, which extends it too.  Growing an
  * image stays out of scope; moving one into a larger slot, and reading
  * metadata and content back out, are in cio_read_dev.h.
  */
