@@ -15,7 +15,9 @@ Layers:
                                                    cio_write_dev_move.h:
                                                    write_metadata / write_at_batch_dev;
                                                    cio_write_dev_records.h:
-                                                   write_records_batch_dev)
+                                                   write_records_batch_dev;
+                                                   cio_write_dev_ungrouped.h:
+                                                   write_records_ungrouped_batch_dev)
                                                    and read path (cio_read_dev.h:
                                                    read / read_packed / meta_cmp_batch_dev)
 """
@@ -32,6 +34,7 @@ from .chunkfile import (  # noqa: F401,E402
     CIOA_READ_CONTENT, CIOA_READ_IMAGE, CIOA_READ_META, CIOA_READ_NUL, CIOA_SEAL_RECOMPUTE, CIOA_WRITER_MOVE,
     DevWriter, init_batch_dev, meta_cmp_batch_dev, read_batch_dev, read_packed_batch_dev, seal_batch_dev,
     verify_batch_dev, write_at_batch_dev, write_batch_dev, write_metadata_batch_dev, write_records_batch_dev,
+    write_records_ungrouped_batch_dev,
 )
 
 __version__ = "0.5.0"

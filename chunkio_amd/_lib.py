@@ -47,6 +47,8 @@ EXPORTS = (
     "cio_file_write_at_batch_dev",
     # include/chunkio_amd/cio_write_dev_records.h
     "cio_file_write_records_batch_dev",
+    # include/chunkio_amd/cio_write_dev_ungrouped.h
+    "cio_file_write_records_ungrouped_batch_dev",
     # include/chunkio_amd/cio_read_dev.h
     "cio_file_read_batch_dev", "cio_file_read_packed_batch_dev", "cio_meta_cmp_batch_dev",
     # include/chunkio_amd/cio_sync.h
@@ -121,6 +123,9 @@ def _bind(lib):
         "cio_file_write_records_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V,
                                                             ctypes.c_uint64, V, V, V, ctypes.c_size_t, ctypes.c_int,
                                                             V, V, V, V]),
+        "cio_file_write_records_ungrouped_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t,
+                                                                      V, ctypes.c_uint64, V, V, V, ctypes.c_size_t,
+                                                                      ctypes.c_int, V, V, V, V, V]),
         "cio_file_read_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int, V,
                                                    V, ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
         "cio_file_read_packed_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int,

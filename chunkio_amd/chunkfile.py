@@ -351,6 +351,35 @@ def write_records_batch_dev(writer, base, img_offs, img_caps, src, rec_img, rec_
     return img_status[:n_img], rec_status[:n_rec]
 
 
+def write_records_ungrouped_batch_dev(writer, base, img_offs, img_caps, src, rec_img, rec_offs, rec_lens, crc_cur,
+                                      flags=CIO_CHECKSUM, img_status=None, rec_status=None, order=None,
+                                      stream=None):
+    """Append record r, src[rec_offs[r]:+rec_lens[r]], to image rec_img[r]
+    (cio_file_write_records_ungrouped_batch_dev): write_records_batch_dev for
+    rec_img in ANY order.  The list is sorted by image on the device, stably:
+    the records of an image are appended in the order in which they appear in
+    the list, and rec_status[r] belongs to record r of the list as given.  Only
+    an index >= n_img is malformed and rejects the whole batch.  order: an
+    optional int32 cuda tensor of n_rec; order[j] becomes the caller's index of
+    the j-th record of the grouped list (the stable argsort of rec_img).
+    Returns (img_status, rec_status) int32 cuda tensors without waiting; pass
+    them in to reuse them (under graph capture)."""
+    from .crc32 import _ptr, _stream_ptr
+    n_img, n_rec = int(img_offs.numel()), int(rec_img.numel())
+    if rec_img.element_size() != 4:
+        raise ValueError("rec_img must be a 32-bit tensor")
+    if order is not None and (order.element_size() != 4 or order.numel() < n_rec):
+        raise ValueError("order must be a 32-bit tensor of n_rec elements")
+    img_status = _status_out(img_status, n_img, base.device)
+    rec_status = _status_out(rec_status, n_rec, base.device)
+    rc = _lib.lib().cio_file_write_records_ungrouped_batch_dev(
+        writer._handle, _ptr(base), base.numel() * base.element_size(), _ptr(img_offs), _ptr(img_caps), n_img,
+        _ptr(src), src.numel() * src.element_size(), _ptr(rec_img), _ptr(rec_offs), _ptr(rec_lens), n_rec,
+        int(flags), _ptr(crc_cur), _ptr(img_status), _ptr(rec_status), _ptr(order), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_write_records_ungrouped_batch_dev")
+    return img_status[:n_img], rec_status[:n_rec]
+
+
 def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM, status=None, stream=None):
     """Seal the images (cio_file_seal_batch_dev): the finalized CRC goes into
     bytes 2..9; with CIOA_SEAL_RECOMPUTE crc_cur is first recomputed from the

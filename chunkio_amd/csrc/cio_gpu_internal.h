@@ -4,8 +4,8 @@
 // read-only stream and the synthetic fill; devplan_gpu.hip: the device
 // planner; write_dev_gpu.hip: the write path of chunk images in HBM;
 // read_dev_gpu.hip: their read path; write_records_gpu.hip: the grouped
-// append; host_pipeline.hip: the host-memory /
-// file batch pipeline).
+// append; sort_records_gpu.hip: the ungrouped append's sort;
+// host_pipeline.hip: the host-memory / file batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
 // planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.
 #ifndef CIOA_GPU_INTERNAL_H
@@ -63,8 +63,8 @@ struct cio_crc32_devplan {
 };
 
 // A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
-// the write path (write_dev_gpu.hip, write_records_gpu.hip) and of the read
-// path (read_dev_gpu.hip).
+// the write path (write_dev_gpu.hip, write_records_gpu.hip,
+// sort_records_gpu.hip) and of the read path (read_dev_gpu.hip).
 struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
     cio_crc32_devplan *dp = nullptr;
@@ -84,6 +84,12 @@ struct cio_dev_writer {
     uint64_t *gsum = nullptr;                // its scan's workgroup aggregates, ceil(max_chunks / kRecBlock)
     uint32_t *gflag = nullptr;
     uint32_t *ghdr = nullptr;                // one word: the batch's grouping is malformed
+    uint32_t *skey[2] = {nullptr, nullptr};  // ungrouped append: the sort's (key, index) arenas, ping-pong
+    uint32_t *sidx[2] = {nullptr, nullptr};
+    uint32_t *stab = nullptr;                // its histogram table, kSortRadix * ceil(max_chunks / kSortBlock)
+    uint32_t *gimg = nullptr;                // the grouped list handed to the grouped append
+    uint64_t *goffs = nullptr, *glens = nullptr;
+    int32_t *gst = nullptr;                  // its record statuses, in grouped order
 };
 
 namespace cioa {
@@ -92,6 +98,14 @@ namespace cioa {
 // (w->soff, w->slen): record i goes from dev_src + w->soff[i] to dev_dst +
 // w->dst[i].  The read path's copy as well: source = the image buffer.
 int launch_copy(const cio_dev_writer *w, void *dev_dst, const void *dev_src, size_t n, hipStream_t s);
+
+// The argument checks of cio_file_write_records_batch_dev and of the ungrouped
+// call that runs it behind a sort (write_records_gpu.hip): 0 go on, 1 a no-op
+// (an empty batch), CIO_ERROR refused, the message under the name `who`.
+int check_records(const char *who, const cio_dev_writer *w, const void *dev_base, const uint64_t *offs,
+                  const uint64_t *caps, size_t n_img, const void *dev_src, const uint32_t *rec_img,
+                  const uint64_t *rec_offs, const uint64_t *rec_lens, size_t n_rec, int flags,
+                  const uint32_t *crc_cur, const int32_t *img_status, const int32_t *rec_status);
 
 }  // namespace cioa
 

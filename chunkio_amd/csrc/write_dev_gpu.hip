@@ -61,6 +61,7 @@
 #include "write_dev_move.h"
 #include "read_dev_place.h"
 #include "write_dev_records.h"
+#include "sort_records.h"
 #include "chunkio_amd/cio_write_dev.h"
 #include "chunkio_amd/cio_write_dev_move.h"
 
@@ -648,6 +649,15 @@ void cio_dev_writer_destroy(cio_dev_writer *w)
     (void) hipFree(w->gsum);
     (void) hipFree(w->gflag);
     (void) hipFree(w->ghdr);
+    (void) hipFree(w->skey[0]);
+    (void) hipFree(w->skey[1]);
+    (void) hipFree(w->sidx[0]);
+    (void) hipFree(w->sidx[1]);
+    (void) hipFree(w->stab);
+    (void) hipFree(w->gimg);
+    (void) hipFree(w->goffs);
+    (void) hipFree(w->glens);
+    (void) hipFree(w->gst);
     delete w;
 }
 
@@ -697,7 +707,16 @@ int cio_dev_writer_create_ex(cio_dev_writer **out, size_t max_chunks, int flags)
         (e = hipMalloc(&w->groom, max_chunks * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMalloc(&w->gsum, ((max_chunks + kRecBlock - 1) / kRecBlock) * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMalloc(&w->gflag, ((max_chunks + kRecBlock - 1) / kRecBlock) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc(&w->ghdr, 2 * sizeof(uint32_t))) != hipSuccess) {
+        (e = hipMalloc(&w->ghdr, 2 * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->skey[0], max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->skey[1], max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->sidx[0], max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->sidx[1], max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->stab, (size_t) kSortRadix * sort_blocks(max_chunks) * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->gimg, max_chunks * sizeof(uint32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->goffs, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->glens, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->gst, max_chunks * sizeof(int32_t))) != hipSuccess) {
         cio_dev_writer_destroy(w);
         return fail("cio_dev_writer_create: device allocation", e);
     }

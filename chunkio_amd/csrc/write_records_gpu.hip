@@ -331,6 +331,13 @@ int launch_bookkeeping(cio_dev_writer *w, const uint8_t *base, uint64_t dev_byte
     return CIO_OK;
 }
 
+}  // namespace
+
+namespace cioa {
+
+// The argument checks of the grouped and the ungrouped append (declared in
+// cio_gpu_internal.h): 0 go on, 1 a no-op, CIO_ERROR refused with a message
+// under the caller's name.
 int check_records(const char *who, const cio_dev_writer *w, const void *dev_base, const uint64_t *offs,
                   const uint64_t *caps, size_t n_img, const void *dev_src, const uint32_t *rec_img,
                   const uint64_t *rec_offs, const uint64_t *rec_lens, size_t n_rec, int flags,
@@ -364,7 +371,7 @@ int check_records(const char *who, const cio_dev_writer *w, const void *dev_base
     return 0;
 }
 
-}  // namespace
+}  // namespace cioa
 
 extern "C" {
 

@@ -67,8 +67,10 @@
  * Preconditions, NOT checked: the images are distinct; source and images do
  * not overlap; one call in flight per writer.
  *
- * Not here: ungrouped record lists (a stable sort by image on the device is
- * the caller's step), growing an image, a CRC per record.
+ * Records in any order: cio_write_dev_ungrouped.h, which sorts the list by
+ * image on the device and then does what this call does.
+ *
+ * Not here: growing an image, a CRC per record.
  */
 #ifndef CIO_WRITE_DEV_RECORDS_H
 #define CIO_WRITE_DEV_RECORDS_H
