@@ -64,6 +64,7 @@ CIOA_SEAL_RECOMPUTE = 256
 CIOA_WRITER_MOVE = 1
 CIOA_READ_META, CIOA_READ_CONTENT, CIOA_READ_IMAGE = 0, 1, 2
 CIOA_READ_NUL = 1
+CIOA_GROW_ZERO = 1              # cio_write_dev_grow.h
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -378,6 +379,56 @@ def write_records_ungrouped_batch_dev(writer, base, img_offs, img_caps, src, rec
         int(flags), _ptr(crc_cur), _ptr(img_status), _ptr(rec_status), _ptr(order), _stream_ptr(stream))
     _lib.check(rc, "cio_file_write_records_ungrouped_batch_dev")
     return img_status[:n_img], rec_status[:n_rec]
+
+
+def _grow_outs(n, dev, total, status):
+    import torch
+    if total is None:
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+    return total, _status_out(status, n, dev)
+
+
+def grow_batch_dev(writer, base, img_offs, img_caps, need, arena, realloc=32768, page=4096, align=16, flags=0,
+                   prev_offs=None, prev_caps=None, total=None, status=None, stream=None):
+    """Grow the images that lack room for need[i] more content bytes
+    (cio_file_grow_batch_dev), queued ahead of an append: such an image gets a
+    slot of the reference's new capacity (cap + k * realloc, rounded up to
+    page) out of the arena, its used bytes are copied there, and img_offs[i] /
+    img_caps[i] are rewritten IN PLACE.  arena: int64 cuda tensor, [0] the top
+    (advanced by the call), [1] the end, offsets into base; align: the slots'
+    alignment, a power of two in 1..4096; flags: 0 or CIOA_GROW_ZERO (zero the
+    new slot behind the used bytes); prev_offs / prev_caps: optional int64
+    cuda tensors of n that receive the entry values.  Returns (status int32,
+    total int64[1]) cuda tensors without waiting: total[0] is what the arena
+    would have to hold for all of them, whether or not it does."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    total, status = _grow_outs(n, base.device, total, status)
+    rc = _lib.lib().cio_file_grow_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(need), _ptr(arena),
+        int(realloc), int(page), int(align), int(flags), _ptr(prev_offs), _ptr(prev_caps), _ptr(total),
+        _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_grow_batch_dev")
+    return status[:n], total
+
+
+def grow_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens, arena, realloc=32768, page=4096,
+                           align=16, flags=0, prev_offs=None, prev_caps=None, total=None, status=None, stream=None):
+    """grow_batch_dev ahead of write_records_batch_dev or its ungrouped form
+    (cio_file_grow_records_batch_dev): the need of image i is the sum of the
+    lengths rec_lens[r] of the records with rec_img[r] == i, in any order,
+    summed on the device.  An index >= n rejects the whole call."""
+    from .crc32 import _ptr, _stream_ptr
+    n, n_rec = int(img_offs.numel()), int(rec_img.numel())
+    if rec_img.element_size() != 4:
+        raise ValueError("rec_img must be a 32-bit tensor")
+    total, status = _grow_outs(n, base.device, total, status)
+    rc = _lib.lib().cio_file_grow_records_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(rec_img),
+        _ptr(rec_lens), n_rec, _ptr(arena), int(realloc), int(page), int(align), int(flags), _ptr(prev_offs),
+        _ptr(prev_caps), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_grow_records_batch_dev")
+    return status[:n], total
 
 
 def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM, status=None, stream=None):

@@ -4,8 +4,9 @@
 // read-only stream and the synthetic fill; devplan_gpu.hip: the device
 // planner; write_dev_gpu.hip: the write path of chunk images in HBM;
 // read_dev_gpu.hip: their read path; write_records_gpu.hip: the grouped
-// append; sort_records_gpu.hip: the ungrouped append's sort;
-// host_pipeline.hip: the host-memory / file batch pipeline).
+// append; sort_records_gpu.hip: the ungrouped append's sort; grow_dev_gpu.hip:
+// growing images out of an arena; host_pipeline.hip: the host-memory / file
+// batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
 // planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.
 #ifndef CIOA_GPU_INTERNAL_H
@@ -64,7 +65,8 @@ struct cio_crc32_devplan {
 
 // A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
 // the write path (write_dev_gpu.hip, write_records_gpu.hip,
-// sort_records_gpu.hip) and of the read path (read_dev_gpu.hip).
+// sort_records_gpu.hip, grow_dev_gpu.hip) and of the read path
+// (read_dev_gpu.hip).
 struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
     cio_crc32_devplan *dp = nullptr;
@@ -90,6 +92,9 @@ struct cio_dev_writer {
     uint32_t *gimg = nullptr;                // the grouped list handed to the grouped append
     uint64_t *goffs = nullptr, *glens = nullptr;
     int32_t *gst = nullptr;                  // its record statuses, in grouped order
+    uint64_t *gneed = nullptr;               // grow: the bytes about to be appended per image (records variant)
+    uint64_t *gcap = nullptr;                // the new capacity of an image that is to grow, 0 otherwise
+    uint32_t *growhdr = nullptr;             // one word: a record's image index lies outside the batch
 };
 
 namespace cioa {

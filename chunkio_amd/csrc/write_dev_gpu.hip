@@ -658,6 +658,9 @@ void cio_dev_writer_destroy(cio_dev_writer *w)
     (void) hipFree(w->goffs);
     (void) hipFree(w->glens);
     (void) hipFree(w->gst);
+    (void) hipFree(w->gneed);
+    (void) hipFree(w->gcap);
+    (void) hipFree(w->growhdr);
     delete w;
 }
 
@@ -716,7 +719,10 @@ int cio_dev_writer_create_ex(cio_dev_writer **out, size_t max_chunks, int flags)
         (e = hipMalloc(&w->gimg, max_chunks * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc(&w->goffs, max_chunks * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMalloc(&w->glens, max_chunks * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipMalloc(&w->gst, max_chunks * sizeof(int32_t))) != hipSuccess) {
+        (e = hipMalloc(&w->gst, max_chunks * sizeof(int32_t))) != hipSuccess ||
+        (e = hipMalloc(&w->gneed, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->gcap, max_chunks * sizeof(uint64_t))) != hipSuccess ||
+        (e = hipMalloc(&w->growhdr, sizeof(uint32_t))) != hipSuccess) {
         cio_dev_writer_destroy(w);
         return fail("cio_dev_writer_create: device allocation", e);
     }

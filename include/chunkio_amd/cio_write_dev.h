@@ -9,15 +9,16 @@
  *                              with metadata, what cio_file_write_metadata /
  *                              adjust_layout (:130-146) leave in an empty chunk
  *   cio_file_write_batch_dev   cio_file_write + update_checksum (:994-1073,
- *                              :97-113) for an image that cannot grow
+ *                              :97-113) for an image of a fixed capacity
+ *                              (cio_write_dev_grow.h grows it first)
  *   cio_file_seal_batch_dev    finalize_checksum (:116-124); with
  *                              CIOA_SEAL_RECOMPUTE the crc_reset path first
  *                              (cio_file_calculate_checksum over the image)
  *
  * An image is a fixed range of a device buffer: image i occupies
- * dev_img_caps[i] bytes at dev_base + dev_img_offs[i] and never grows (the
- * reference's realloc has no device counterpart: an append that does not fit
- * is rejected).  Its layout is the chunk file's: magic C1 00, CRC bytes 2..9,
+ * dev_img_caps[i] bytes at dev_base + dev_img_offs[i] and none of these calls
+ * grows it: an append that does not fit is rejected (the reference's resize
+ * is a call of its own, queued ahead of the append: cio_write_dev_grow.h).  Its layout is the chunk file's: magic C1 00, CRC bytes 2..9,
  * content length big-endian at 10..13, metadata length big-endian at 22..23,
  * metadata from byte 24, content after it.
  *
@@ -56,8 +57,9 @@
  * it: both are in cio_write_dev_move.h, which extends this header.  Appending
  * MANY records to an image in one call (these calls take at most one per
  * image) is in cio_write_dev_records.h, which extends it too.  Growing an
- * image stays out of scope; moving one into a larger slot, and reading
- * metadata and content back out, are in cio_read_dev.h.
+ * image out of an arena ahead of an append is in cio_write_dev_grow.h; moving
+ * one into a slot the host chose, and reading metadata and content back out,
+ * are in cio_read_dev.h.
  */
 #ifndef CIO_WRITE_DEV_H
 #define CIO_WRITE_DEV_H

@@ -13,8 +13,9 @@
  *                                       184-209): the crc_reset recompute over
  *                                       the kept prefix, then cio_file_write
  *
- * An image still never grows: an entry that does not fit its capacity is
- * rejected.  A rejected entry changes no byte of its image and not its
+ * These calls never grow an image: an entry that does not fit its capacity is
+ * rejected (cio_write_dev_grow.h grows images ahead of a call; for a longer
+ * metadata the caller passes the difference of the lengths as the need).  A rejected entry changes no byte of its image and not its
  * dev_crc_cur[i].
  */
 #ifndef CIO_WRITE_DEV_MOVE_H

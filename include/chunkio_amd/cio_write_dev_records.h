@@ -70,7 +70,8 @@
  * Records in any order: cio_write_dev_ungrouped.h, which sorts the list by
  * image on the device and then does what this call does.
  *
- * Not here: growing an image, a CRC per record.
+ * Not here: a CRC per record.  Growing the images for a record list is
+ * cio_file_grow_records_batch_dev (cio_write_dev_grow.h), queued ahead.
  */
 #ifndef CIO_WRITE_DEV_RECORDS_H
 #define CIO_WRITE_DEV_RECORDS_H

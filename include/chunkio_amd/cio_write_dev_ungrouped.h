@@ -41,7 +41,9 @@
  * grouped chain; a caller whose list is already grouped calls
  * cio_file_write_records_batch_dev.
  *
- * Not here: growing an image, a CRC per record, per-record destinations.
+ * Not here: a CRC per record, per-record destinations.  Growing the images for
+ * a record list is cio_file_grow_records_batch_dev (cio_write_dev_grow.h),
+ * queued ahead; it takes the list in any order too.
  */
 #ifndef CIO_WRITE_DEV_UNGROUPED_H
 #define CIO_WRITE_DEV_UNGROUPED_H
