@@ -431,6 +431,72 @@ def grow_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens, 
     return status[:n], total
 
 
+def _rotate_outs(n, dev, out_offs, out_caps, out_img, out_count, total, status):
+    import torch
+    if out_count is None:
+        out_count = torch.tensor([0, max(n, 1)], dtype=torch.int64, device=dev)
+    if out_offs is None:
+        out_offs = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    if out_caps is None:
+        out_caps = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    if out_img is None:
+        out_img = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    if total is None:
+        total = torch.zeros(2, dtype=torch.int64, device=dev)
+    return out_offs, out_caps, out_img, out_count, total, _status_out(status, n, dev)
+
+
+def rotate_batch_dev(writer, base, img_offs, img_caps, need, limit=0, new_cap=None, align=16, arena=None,
+                     out_offs=None, out_caps=None, out_img=None, out_count=None, flags=CIO_CHECKSUM, crc_cur=None,
+                     total=None, status=None, stream=None):
+    """Finish the images that are full and open the next ones
+    (cio_file_rotate_batch_dev), queued ahead of a grow and an append: an
+    image with content that lacks room for need[i] more bytes, or would hold
+    more than `limit` content bytes with them (limit 0: no limit), is sealed
+    where it lies and entered into the list of finished chunks (out_offs,
+    out_caps, out_img; out_count: int64 cuda tensor, [0] the entries in it,
+    advanced by the call, [1] its capacity); a fresh image of new_cap bytes
+    with the same metadata is built in a slot of the arena (int64 cuda tensor,
+    [0] the top, advanced, [1] the end), and img_offs[i], img_caps[i] and
+    crc_cur[i] are rewritten IN PLACE.  need: int64 cuda tensor or None (every
+    need 0); flags: 0 or CIO_CHECKSUM.  The list tensors are made, for n
+    entries and empty, when not given.  Returns (status int32, total int64[2],
+    out_offs, out_caps, out_img, out_count) cuda tensors without waiting:
+    total[0] is what the arena would have to hold for all full images and
+    total[1] their number, whether or not arena and list take them."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    out_offs, out_caps, out_img, out_count, total, status = _rotate_outs(
+        n, base.device, out_offs, out_caps, out_img, out_count, total, status)
+    rc = _lib.lib().cio_file_rotate_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(need), int(limit),
+        int(new_cap), int(align), _ptr(arena), _ptr(out_offs), _ptr(out_caps), _ptr(out_img), _ptr(out_count),
+        int(flags), _ptr(crc_cur), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_rotate_batch_dev")
+    return status[:n], total, out_offs, out_caps, out_img, out_count
+
+
+def rotate_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens, limit=0, new_cap=None, align=16,
+                             arena=None, out_offs=None, out_caps=None, out_img=None, out_count=None,
+                             flags=CIO_CHECKSUM, crc_cur=None, total=None, status=None, stream=None):
+    """rotate_batch_dev ahead of write_records_batch_dev or its ungrouped form
+    (cio_file_rotate_records_batch_dev): the need of image i is the sum of the
+    lengths rec_lens[r] of the records with rec_img[r] == i, in any order,
+    summed on the device.  An index >= n rejects the whole call."""
+    from .crc32 import _ptr, _stream_ptr
+    n, n_rec = int(img_offs.numel()), int(rec_img.numel())
+    if rec_img.element_size() != 4:
+        raise ValueError("rec_img must be a 32-bit tensor")
+    out_offs, out_caps, out_img, out_count, total, status = _rotate_outs(
+        n, base.device, out_offs, out_caps, out_img, out_count, total, status)
+    rc = _lib.lib().cio_file_rotate_records_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(rec_img),
+        _ptr(rec_lens), n_rec, int(limit), int(new_cap), int(align), _ptr(arena), _ptr(out_offs), _ptr(out_caps),
+        _ptr(out_img), _ptr(out_count), int(flags), _ptr(crc_cur), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_rotate_records_batch_dev")
+    return status[:n], total, out_offs, out_caps, out_img, out_count
+
+
 def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM, status=None, stream=None):
     """Seal the images (cio_file_seal_batch_dev): the finalized CRC goes into
     bytes 2..9; with CIOA_SEAL_RECOMPUTE crc_cur is first recomputed from the

@@ -5,7 +5,8 @@
 // planner; write_dev_gpu.hip: the write path of chunk images in HBM;
 // read_dev_gpu.hip: their read path; write_records_gpu.hip: the grouped
 // append; sort_records_gpu.hip: the ungrouped append's sort; grow_dev_gpu.hip:
-// growing images out of an arena; host_pipeline.hip: the host-memory / file
+// growing images out of an arena; rotate_dev_gpu.hip: rotating full images;
+// host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
 // planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.
@@ -65,7 +66,7 @@ struct cio_crc32_devplan {
 
 // A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
 // the write path (write_dev_gpu.hip, write_records_gpu.hip,
-// sort_records_gpu.hip, grow_dev_gpu.hip) and of the read path
+// sort_records_gpu.hip, grow_dev_gpu.hip, rotate_dev_gpu.hip) and of the read path
 // (read_dev_gpu.hip).
 struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
