@@ -53,6 +53,9 @@ EXPORTS = (
     "cio_file_grow_batch_dev", "cio_file_grow_records_batch_dev",
     # include/chunkio_amd/cio_write_dev_rotate.h
     "cio_file_rotate_batch_dev", "cio_file_rotate_records_batch_dev",
+    # include/chunkio_amd/cio_write_dev_tx.h
+    "cio_file_tx_begin_batch_dev", "cio_file_tx_rollback_batch_dev", "cio_file_tx_commit_batch_dev",
+    "cio_file_tx_cond_records_batch_dev",
     # include/chunkio_amd/cio_read_dev.h
     "cio_file_read_batch_dev", "cio_file_read_packed_batch_dev", "cio_meta_cmp_batch_dev",
     # include/chunkio_amd/cio_sync.h
@@ -143,6 +146,13 @@ def _bind(lib):
                                                              ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
                                                              ctypes.c_uint64, V, V, V, V, V, ctypes.c_int, V, V, V,
                                                              V]),
+        "cio_file_tx_begin_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int, V, V,
+                                                       V, V]),
+        "cio_file_tx_rollback_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V,
+                                                          ctypes.c_int, V, V, V, V]),
+        "cio_file_tx_commit_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V,
+                                                        ctypes.c_int, V, V, V, V]),
+        "cio_file_tx_cond_records_batch_dev": (ctypes.c_int, [V, V, ctypes.c_size_t, V, ctypes.c_size_t, V, V]),
         "cio_file_read_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int, V,
                                                    V, ctypes.c_uint64, V, V, ctypes.c_int, V, V, V]),
         "cio_file_read_packed_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int,

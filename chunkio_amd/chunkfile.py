@@ -42,6 +42,12 @@ read_batch_dev / read_packed_batch_dev gather the metadata, the content or the
 trimmed image of every image of a batch into an output tensor
 (cio_meta_read, cio_file_content_copy; include/chunkio_amd/cio_read_dev.h),
 and meta_cmp_batch_dev is cio_meta_cmp.
+
+tx_state with tx_begin_batch_dev / tx_rollback_batch_dev / tx_commit_batch_dev
+are cio_chunk_tx_begin / _rollback / _commit (src/cio_chunk.c:423-502) on
+images in device memory, and tx_cond_records_batch_dev turns the statuses of a
+records append into the per-image condition of an all-or-nothing append
+(include/chunkio_amd/cio_write_dev_tx.h).
 """
 import ctypes
 import os
@@ -65,6 +71,7 @@ CIOA_WRITER_MOVE = 1
 CIOA_READ_META, CIOA_READ_CONTENT, CIOA_READ_IMAGE = 0, 1, 2
 CIOA_READ_NUL = 1
 CIOA_GROW_ZERO = 1              # cio_write_dev_grow.h
+CIOA_TX_RECOMPUTE, CIOA_TX_ZERO = 256, 512      # cio_write_dev_tx.h
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -495,6 +502,92 @@ def rotate_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens
         _ptr(out_img), _ptr(out_count), int(flags), _ptr(crc_cur), _ptr(total), _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_rotate_records_batch_dev")
     return status[:n], total, out_offs, out_caps, out_img, out_count
+
+
+def tx_state(n, device):
+    """The transaction state of n images (cio_dev_tx_state, 16 bytes each): an
+    int32 cuda tensor of shape (n, 4) -- active, content_len, crc, meta_len --
+    zeroed: no transaction active."""
+    import torch
+    return torch.zeros((max(int(n), 1), 4), dtype=torch.int32, device=device)[:int(n)]
+
+
+def tx_begin_batch_dev(writer, base, img_offs, img_caps, tx, crc_cur=None, flags=CIO_CHECKSUM, status=None,
+                       stream=None):
+    """Begin a transaction on every image (cio_file_tx_begin_batch_dev): entry
+    i of tx (from tx_state) takes the image's content and metadata lengths and,
+    with CIO_CHECKSUM, crc_cur[i]; an entry that is already active is left
+    alone.  No image byte is written.  Returns the status cuda tensor (int32)
+    without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_tx_begin_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, int(flags), _ptr(crc_cur),
+        _ptr(tx), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_tx_begin_batch_dev")
+    return status[:n]
+
+
+def tx_rollback_batch_dev(writer, base, img_offs, img_caps, tx, crc_cur=None, cond=None, flags=CIO_CHECKSUM,
+                          status=None, stream=None):
+    """Roll the images back to where they were at tx_begin_batch_dev
+    (cio_file_tx_rollback_batch_dev): the content length and, with
+    CIO_CHECKSUM, crc_cur and the header's CRC bytes.  cond: optional int32
+    cuda tensor of n; entries with cond[i] == CIO_OK are skipped.  flags: 0,
+    CIO_CHECKSUM, with it CIOA_TX_RECOMPUTE (crc_cur is recomputed from the
+    image: needed after write_at or a metadata rewrite inside the
+    transaction), and CIOA_TX_ZERO (the dropped bytes become zero).  An entry
+    that is not active, or whose image shrank inside the transaction, gets
+    CIO_ERROR.  Returns the status cuda tensor (int32) without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_tx_rollback_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(cond), int(flags),
+        _ptr(crc_cur), _ptr(tx), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_tx_rollback_batch_dev")
+    return status[:n]
+
+
+def tx_commit_batch_dev(writer, base, img_offs, img_caps, tx, crc_cur=None, cond=None, flags=CIO_CHECKSUM,
+                        status=None, stream=None):
+    """Commit the images (cio_file_tx_commit_batch_dev): with CIO_CHECKSUM
+    they are sealed as seal_batch_dev does it, and their entries of tx become
+    inactive.  cond: optional int32 cuda tensor of n; only entries with cond[i]
+    == CIO_OK are acted on, so the same cond given to tx_rollback_batch_dev and
+    to this call handles every image exactly once.  Returns the status cuda
+    tensor (int32) without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_tx_commit_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(cond), int(flags),
+        _ptr(crc_cur), _ptr(tx), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_tx_commit_batch_dev")
+    return status[:n]
+
+
+def tx_cond_records_batch_dev(rec_img, rec_status, n_img, img_status=None, cond=None, stream=None):
+    """The per-image condition of an all-or-nothing append
+    (cio_file_tx_cond_records_batch_dev): cond[i] is CIO_ERROR iff a record of
+    image i has rec_status != CIO_OK or img_status[i] != CIO_OK, for records in
+    any order; an index >= n_img makes every entry CIO_ERROR.  rec_img,
+    rec_status: 32-bit cuda tensors (or None: no records).  Returns the cond
+    cuda tensor (int32 of n_img) without waiting; pass `cond` to reuse one."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n_img = int(n_img)
+    n_rec = 0 if rec_img is None else int(rec_img.numel())
+    if n_rec and (rec_img.element_size() != 4 or rec_status.element_size() != 4 or rec_status.numel() < n_rec):
+        raise ValueError("rec_img and rec_status must be 32-bit tensors of n_rec elements")
+    if cond is None:
+        dev = rec_img.device if rec_img is not None else img_status.device
+        cond = torch.zeros(max(n_img, 1), dtype=torch.int32, device=dev)
+    rc = _lib.lib().cio_file_tx_cond_records_batch_dev(_ptr(rec_img), _ptr(rec_status), n_rec, _ptr(img_status),
+                                                       n_img, _ptr(cond), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_tx_cond_records_batch_dev")
+    return cond[:n_img]
 
 
 def seal_batch_dev(writer, base, img_offs, img_caps, crc_cur, flags=CIO_CHECKSUM, status=None, stream=None):

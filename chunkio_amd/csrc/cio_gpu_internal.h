@@ -6,6 +6,7 @@
 // read_dev_gpu.hip: their read path; write_records_gpu.hip: the grouped
 // append; sort_records_gpu.hip: the ungrouped append's sort; grow_dev_gpu.hip:
 // growing images out of an arena; rotate_dev_gpu.hip: rotating full images;
+// tx_dev_gpu.hip: transactions on images;
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
@@ -66,7 +67,7 @@ struct cio_crc32_devplan {
 
 // A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
 // the write path (write_dev_gpu.hip, write_records_gpu.hip,
-// sort_records_gpu.hip, grow_dev_gpu.hip, rotate_dev_gpu.hip) and of the read path
+// sort_records_gpu.hip, grow_dev_gpu.hip, rotate_dev_gpu.hip, tx_dev_gpu.hip) and of the read path
 // (read_dev_gpu.hip).
 struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
@@ -104,6 +105,12 @@ namespace cioa {
 // (w->soff, w->slen): record i goes from dev_src + w->soff[i] to dev_dst +
 // w->dst[i].  The read path's copy as well: source = the image buffer.
 int launch_copy(const cio_dev_writer *w, void *dev_dst, const void *dev_src, size_t n, hipStream_t s);
+
+// One launch of grow's byte-balanced zero fill (grow_dev_gpu.hip) over the
+// planner's image of (zoff, zlen): region i, zlen[i] bytes at dev_base +
+// zoff[i], becomes zero.  The transaction rollback's fill as well.
+int launch_zero_fill(const cio_dev_writer *w, void *dev_base, const uint64_t *zoff, const uint64_t *zlen, size_t n,
+                     hipStream_t s);
 
 // The argument checks of cio_file_write_records_batch_dev and of the ungrouped
 // call that runs it behind a sort (write_records_gpu.hip): 0 go on, 1 a no-op

@@ -412,10 +412,8 @@ int launch_grow(const GrowArgs &a, hipStream_t s, const GrowEvents *ev)
             mark(ev, kSecZero, true, s) != CIO_OK) {
             return CIO_ERROR;
         }
-        hipLaunchKernelGGL(grow_zero, dim3(w->copy_grid), dim3(kZeroThreads), 0, s, base, w->dp->p->desc, w->roff,
-                           w->rlen, w->dp->hdr, n);
-        HIP_TRY(hipGetLastError(), "grow: zero kernel launch");
-        if (mark(ev, kSecZero, false, s) != CIO_OK) {
+        if (launch_zero_fill(w, a.dev_base, w->roff, w->rlen, a.n, s) != CIO_OK ||
+            mark(ev, kSecZero, false, s) != CIO_OK) {
             return CIO_ERROR;
         }
     }
@@ -429,6 +427,18 @@ int launch_grow(const GrowArgs &a, hipStream_t s, const GrowEvents *ev)
 }
 
 }  // namespace
+
+// One launch of grow_zero over the planner's image of (zoff, zlen): region i,
+// zlen[i] bytes at dev_base + zoff[i], becomes zero.  The rollback's fill as
+// well (tx_dev_gpu.hip).
+int cioa::launch_zero_fill(const cio_dev_writer *w, void *dev_base, const uint64_t *zoff, const uint64_t *zlen, size_t n,
+                           hipStream_t s)
+{
+    hipLaunchKernelGGL(grow_zero, dim3(w->copy_grid), dim3(kZeroThreads), 0, s, reinterpret_cast<uint8_t *>(dev_base),
+                       w->dp->p->desc, zoff, zlen, w->dp->hdr, (uint32_t) n);
+    HIP_TRY(hipGetLastError(), "zero fill kernel launch");
+    return CIO_OK;
+}
 
 extern "C" {
 
