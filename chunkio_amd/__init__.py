@@ -22,6 +22,10 @@ Layers:
                                                    grow_batch_dev / grow_records_batch_dev;
                                                    cio_write_dev_rotate.h:
                                                    rotate_batch_dev / rotate_records_batch_dev;
+                                                   cio_write_dev_pool.h:
+                                                   pool_state, release_batch_dev,
+                                                   rotate_pool_batch_dev /
+                                                   rotate_pool_records_batch_dev;
                                                    cio_write_dev_tx.h:
                                                    tx_state, tx_begin / tx_rollback /
                                                    tx_commit / tx_cond_records_batch_dev)
@@ -41,6 +45,8 @@ from .chunkfile import (  # noqa: F401,E402
     CIOA_GROW_ZERO, CIOA_TX_RECOMPUTE, CIOA_TX_ZERO, CIOA_READ_CONTENT, CIOA_READ_IMAGE, CIOA_READ_META, CIOA_READ_NUL, CIOA_SEAL_RECOMPUTE, CIOA_WRITER_MOVE,
     DevWriter, grow_batch_dev, grow_records_batch_dev, init_batch_dev, meta_cmp_batch_dev, read_batch_dev, read_packed_batch_dev,
     rotate_batch_dev, rotate_records_batch_dev, seal_batch_dev,
+    CIOA_RELEASE_COMPACT, CIOA_RELEASE_ZERO, pool_state, release_batch_dev, rotate_pool_batch_dev,
+    rotate_pool_records_batch_dev,
     tx_begin_batch_dev, tx_commit_batch_dev, tx_cond_records_batch_dev, tx_rollback_batch_dev, tx_state,
     verify_batch_dev, write_at_batch_dev, write_batch_dev, write_metadata_batch_dev, write_records_batch_dev,
     write_records_ungrouped_batch_dev,

@@ -72,6 +72,7 @@ CIOA_READ_META, CIOA_READ_CONTENT, CIOA_READ_IMAGE = 0, 1, 2
 CIOA_READ_NUL = 1
 CIOA_GROW_ZERO = 1              # cio_write_dev_grow.h
 CIOA_TX_RECOMPUTE, CIOA_TX_ZERO = 256, 512      # cio_write_dev_tx.h
+CIOA_RELEASE_ZERO, CIOA_RELEASE_COMPACT = 1, 2  # cio_write_dev_pool.h
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -501,6 +502,95 @@ def rotate_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens
         _ptr(rec_lens), n_rec, int(limit), int(new_cap), int(align), _ptr(arena), _ptr(out_offs), _ptr(out_caps),
         _ptr(out_img), _ptr(out_count), int(flags), _ptr(crc_cur), _ptr(total), _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_rotate_records_batch_dev")
+    return status[:n], total, out_offs, out_caps, out_img, out_count
+
+
+def pool_state(capacity, cls, align, device):
+    """An empty pool of free slots (cio_write_dev_pool.h): (pool_offs,
+    pool_caps, pool) int64 cuda tensors -- the two arrays of `capacity`
+    entries and the four words [entries, capacity, cls, align]: every slot
+    released into the pool has at least cls bytes at a multiple of align."""
+    import torch
+    offs = torch.zeros(max(int(capacity), 1), dtype=torch.int64, device=device)
+    caps = torch.zeros(max(int(capacity), 1), dtype=torch.int64, device=device)
+    pool = torch.tensor([0, int(capacity), int(cls), int(align)], dtype=torch.int64, device=device)
+    return offs, caps, pool
+
+
+def release_batch_dev(writer, base, offs, caps, pool_offs, pool_caps, pool, img=None, count=None, gate=None,
+                      live_offs=None, flags=0, total=None, status=None, stream=None):
+    """Give the slots of drained chunks back to a pool
+    (cio_file_release_batch_dev).  offs / caps (/ img): rotate's list of
+    finished chunks, or grow's prev_offs / prev_caps; count: the list's
+    out_count (only the first min(n, count[0]) entries are looked at); gate:
+    int32 statuses, an entry whose gate is not CIO_OK is kept (pass the packed
+    read's status); live_offs: an entry whose offset equals live_offs[i] is
+    kept (pass img_offs behind a grow).  A slot that passes the image check and
+    fits the pool's class and alignment is pushed while the pool has room, and
+    its bytes 0..1 are zeroed; flags: CIOA_RELEASE_ZERO zeroes the whole slot,
+    CIOA_RELEASE_COMPACT moves the kept entries to the front of the list IN
+    PLACE and sets count[0].  Returns (status int32, total int64[2]) cuda
+    tensors without waiting: total[0] the entries that were releasable,
+    whatever the pool's room, total[1] the entries kept."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(offs.numel())
+    if img is not None and img.element_size() != 4:
+        raise ValueError("img must be a 32-bit tensor")
+    if total is None:
+        total = torch.zeros(2, dtype=torch.int64, device=base.device)
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_release_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(offs), _ptr(caps), _ptr(img), n, _ptr(count), _ptr(gate),
+        _ptr(live_offs), int(flags), _ptr(pool_offs), _ptr(pool_caps), _ptr(pool), _ptr(total), _ptr(status),
+        _stream_ptr(stream))
+    _lib.check(rc, "cio_file_release_batch_dev")
+    return status[:n], total
+
+
+def rotate_pool_batch_dev(writer, base, img_offs, img_caps, need, limit=0, new_cap=None, align=16, arena=None,
+                          pool_offs=None, pool_caps=None, pool=None, out_offs=None, out_caps=None, out_img=None,
+                          out_count=None, flags=CIO_CHECKSUM, crc_cur=None, total=None, status=None, stream=None):
+    """rotate_batch_dev that takes the fresh slots from a pool of released
+    slots before it touches the arena (cio_file_rotate_pool_batch_dev): the
+    first pool[0] full images -- when the pool is sound, new_cap <= its class
+    and its alignment a multiple of align -- get the pool's top entries, with
+    the entry's whole capacity in img_caps[i]; the others arena slots as in
+    rotate_batch_dev.  pool_offs, pool_caps, pool: from pool_state, filled by
+    release_batch_dev; pool[0] is lowered by the call.  Returns what
+    rotate_batch_dev returns; total[0] counts the arena bytes only."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    out_offs, out_caps, out_img, out_count, total, status = _rotate_outs(
+        n, base.device, out_offs, out_caps, out_img, out_count, total, status)
+    rc = _lib.lib().cio_file_rotate_pool_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(need), int(limit),
+        int(new_cap), int(align), _ptr(arena), _ptr(pool_offs), _ptr(pool_caps), _ptr(pool), _ptr(out_offs),
+        _ptr(out_caps), _ptr(out_img), _ptr(out_count), int(flags), _ptr(crc_cur), _ptr(total), _ptr(status),
+        _stream_ptr(stream))
+    _lib.check(rc, "cio_file_rotate_pool_batch_dev")
+    return status[:n], total, out_offs, out_caps, out_img, out_count
+
+
+def rotate_pool_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens, limit=0, new_cap=None,
+                                  align=16, arena=None, pool_offs=None, pool_caps=None, pool=None, out_offs=None,
+                                  out_caps=None, out_img=None, out_count=None, flags=CIO_CHECKSUM, crc_cur=None,
+                                  total=None, status=None, stream=None):
+    """rotate_pool_batch_dev ahead of write_records_batch_dev or its ungrouped
+    form (cio_file_rotate_pool_records_batch_dev): the needs are summed on the
+    device from the record list, as in rotate_records_batch_dev."""
+    from .crc32 import _ptr, _stream_ptr
+    n, n_rec = int(img_offs.numel()), int(rec_img.numel())
+    if rec_img.element_size() != 4:
+        raise ValueError("rec_img must be a 32-bit tensor")
+    out_offs, out_caps, out_img, out_count, total, status = _rotate_outs(
+        n, base.device, out_offs, out_caps, out_img, out_count, total, status)
+    rc = _lib.lib().cio_file_rotate_pool_records_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(rec_img),
+        _ptr(rec_lens), n_rec, int(limit), int(new_cap), int(align), _ptr(arena), _ptr(pool_offs), _ptr(pool_caps),
+        _ptr(pool), _ptr(out_offs), _ptr(out_caps), _ptr(out_img), _ptr(out_count), int(flags), _ptr(crc_cur),
+        _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_rotate_pool_records_batch_dev")
     return status[:n], total, out_offs, out_caps, out_img, out_count
 
 

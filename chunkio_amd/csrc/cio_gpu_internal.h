@@ -6,7 +6,8 @@
 // read_dev_gpu.hip: their read path; write_records_gpu.hip: the grouped
 // append; sort_records_gpu.hip: the ungrouped append's sort; grow_dev_gpu.hip:
 // growing images out of an arena; rotate_dev_gpu.hip: rotating full images;
-// tx_dev_gpu.hip: transactions on images;
+// tx_dev_gpu.hip: transactions on images; pool_dev_gpu.hip: recycling drained
+// slots through a pool;
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
@@ -67,7 +68,7 @@ struct cio_crc32_devplan {
 
 // A writer of chunk images in HBM (cio_write_dev.h): the per-batch workspace of
 // the write path (write_dev_gpu.hip, write_records_gpu.hip,
-// sort_records_gpu.hip, grow_dev_gpu.hip, rotate_dev_gpu.hip, tx_dev_gpu.hip) and of the read path
+// sort_records_gpu.hip, grow_dev_gpu.hip, rotate_dev_gpu.hip, tx_dev_gpu.hip, pool_dev_gpu.hip) and of the read path
 // (read_dev_gpu.hip).
 struct cio_dev_writer {
     uint32_t max_chunks = 0;                 // first: the argument checks read it
@@ -119,6 +120,40 @@ int check_records(const char *who, const cio_dev_writer *w, const void *dev_base
                   const uint64_t *caps, size_t n_img, const void *dev_src, const uint32_t *rec_img,
                   const uint64_t *rec_offs, const uint64_t *rec_lens, size_t n_rec, int flags,
                   const uint32_t *crc_cur, const int32_t *img_status, const int32_t *rec_status);
+
+// The arguments of a rotate call (rotate_dev_gpu.hip; the calls that take the
+// fresh slots from a pool first, pool_dev_gpu.hip, share them).
+struct RotArgs {
+    const char *who;
+    cio_dev_writer *w;
+    void *dev_base;
+    uint64_t dev_bytes;
+    uint64_t *offs, *caps;
+    size_t n;
+    const uint64_t *need;                     // the need variant; may be NULL there too
+    const uint32_t *rec_img;
+    const uint64_t *rec_lens;
+    size_t n_rec;
+    uint64_t limit, new_cap, align;
+    uint64_t *arena, *out_offs, *out_caps;
+    uint32_t *out_img;
+    uint64_t *out_count;
+    int flags;
+    uint32_t *crc_cur;
+    uint64_t *total;
+    int32_t *status;
+};
+
+// The argument checks of the rotate calls, before any device call
+// (rotate_dev_gpu.hip): 0 go on, 1 a no-op (an empty batch), CIO_ERROR refused.
+int rotate_check_args(const RotArgs &a, bool records);
+
+// The head of a rotate batch, unchanged, for the pool variant: rotate_clear and
+// rotate_sums (records), rotate_headers and rotate_scan.  Leaves in the
+// writer's arenas gcap = 24 + meta of an image that reaches the placement (0
+// otherwise), groom its ordinal in its workgroup, rtot the workgroups'
+// exclusive counts, seed the CRC states, and in a.total rotate's dev_total.
+int rotate_launch_front(const RotArgs &a, bool records, hipStream_t s);
 
 }  // namespace cioa
 

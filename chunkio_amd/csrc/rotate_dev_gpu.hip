@@ -338,27 +338,6 @@ uint32_t blocks_of(size_t n, uint32_t per)
     return (uint32_t) ((n + per - 1) / per);
 }
 
-struct RotArgs {
-    const char *who;
-    cio_dev_writer *w;
-    void *dev_base;
-    uint64_t dev_bytes;
-    uint64_t *offs, *caps;
-    size_t n;
-    const uint64_t *need;                     // the need variant; may be NULL there too
-    const uint32_t *rec_img;
-    const uint64_t *rec_lens;
-    size_t n_rec;
-    uint64_t limit, new_cap, align;
-    uint64_t *arena, *out_offs, *out_caps;
-    uint32_t *out_img;
-    uint64_t *out_count;
-    int flags;
-    uint32_t *crc_cur;
-    uint64_t *total;
-    int32_t *status;
-};
-
 bool pow2(uint64_t v)
 {
     return v != 0 && (v & (v - 1)) == 0;
@@ -485,6 +464,34 @@ int launch_rotate(const RotArgs &a, bool records, hipStream_t s, const RotEvents
 }
 
 }  // namespace
+
+int cioa::rotate_check_args(const RotArgs &a, bool records)
+{
+    return check_rotate(a, records);
+}
+
+// launch_rotate up to rotate_scan, without the measurement marks.
+int cioa::rotate_launch_front(const RotArgs &a, bool records, hipStream_t s)
+{
+    cio_dev_writer *w = a.w;
+    const uint32_t n = (uint32_t) a.n, nb = blocks_of(a.n, kRotBlock);
+    const uint64_t *need = a.need;
+    if (records) {
+        unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
+        hipLaunchKernelGGL(rotate_clear, dim3(blocks_of(a.n, 256)), dim3(256), 0, s, acc, n, w->growhdr);
+        hipLaunchKernelGGL(rotate_sums, dim3(blocks_of(a.n_rec, kRotSumBlock)), dim3(kRotSumBlock), 0, s, a.rec_img,
+                           a.rec_lens, (uint32_t) a.n_rec, n, acc, w->growhdr);
+        HIP_TRY(hipGetLastError(), "rotate: sums kernels launch");
+        need = w->gneed;
+    }
+    hipLaunchKernelGGL(rotate_headers, dim3(nb), dim3(kRotBlock), 0, s, reinterpret_cast<const uint8_t *>(a.dev_base),
+                       a.dev_bytes, a.offs, a.caps, n, need, records ? w->growhdr : (const uint32_t *) nullptr,
+                       a.arena, a.limit, a.new_cap, a.status, w->gcap, w->groom, w->seed, w->rtot);
+    hipLaunchKernelGGL(rotate_scan, dim3(1), dim3(kRotBlock), 0, s, w->rtot, nb, a.arena, a.new_cap, a.align,
+                       a.total);
+    HIP_TRY(hipGetLastError(), "rotate: header kernels launch");
+    return CIO_OK;
+}
 
 extern "C" {
 

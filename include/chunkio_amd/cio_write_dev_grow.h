@@ -77,8 +77,11 @@
  * call in flight per writer), and the arena's free part shares no byte with
  * anything the caller still needs.
  *
- * Not here: reusing freed slots (a device-side free list or compaction -- a
- * packed CIOA_READ_IMAGE read into a fresh buffer already compacts);
+ * Not here: reusing freed slots -- cio_write_dev_pool.h releases the previous
+ * slots (dev_prev_offs / dev_prev_caps with dev_live_offs = dev_img_offs) to a
+ * device-side pool that the next rotation takes from; grow itself keeps
+ * taking from the arena (and a packed CIOA_READ_IMAGE read into a fresh buffer
+ * still compacts);
  * extending in place an image that ends at top; growth for
  * cio_file_write_metadata_batch_dev (the caller passes the metadata delta as
  * the need and grows first); fusing the grow into the append kernels.

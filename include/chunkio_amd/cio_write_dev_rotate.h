@@ -90,8 +90,11 @@
  * anything the caller still needs), and the three list arrays hold
  * dev_out_count[1] entries each.
  *
- * Not here: zeroing the fresh slot's tail; freeing or reusing the slots of
- * the sealed chunks (the caller owns them once they are in the list);
+ * Not here: zeroing the fresh slot's tail, and freeing or reusing the slots of
+ * the sealed chunks (the caller owns them once they are in the list) -- both
+ * are cio_write_dev_pool.h: cio_file_release_batch_dev gives a drained chunk's
+ * slot back to a pool, zeroed if asked, and cio_file_rotate_pool_batch_dev
+ * takes the fresh slots from that pool before the arena;
  * per-image new capacities -- a caller queues cio_file_grow_batch_dev behind
  * this call, and grow extends a fresh image whose need does not fit new_cap.
  */
