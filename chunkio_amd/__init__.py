@@ -26,6 +26,10 @@ Layers:
                                                    pool_state, release_batch_dev,
                                                    rotate_pool_batch_dev /
                                                    rotate_pool_records_batch_dev;
+                                                   cio_write_dev_pool_set.h:
+                                                   pool_set_state, pool_set_class,
+                                                   release_set_batch_dev, grow_set_batch_dev /
+                                                   grow_set_records_batch_dev;
                                                    cio_write_dev_tx.h:
                                                    tx_state, tx_begin / tx_rollback /
                                                    tx_commit / tx_cond_records_batch_dev)
@@ -47,6 +51,8 @@ from .chunkfile import (  # noqa: F401,E402
     rotate_batch_dev, rotate_records_batch_dev, seal_batch_dev,
     CIOA_RELEASE_COMPACT, CIOA_RELEASE_ZERO, pool_state, release_batch_dev, rotate_pool_batch_dev,
     rotate_pool_records_batch_dev,
+    CIOA_POOL_SET_MAX, grow_set_batch_dev, grow_set_records_batch_dev, pool_set_class, pool_set_state,
+    release_set_batch_dev,
     tx_begin_batch_dev, tx_commit_batch_dev, tx_cond_records_batch_dev, tx_rollback_batch_dev, tx_state,
     verify_batch_dev, write_at_batch_dev, write_batch_dev, write_metadata_batch_dev, write_records_batch_dev,
     write_records_ungrouped_batch_dev,

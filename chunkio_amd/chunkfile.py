@@ -73,6 +73,7 @@ CIOA_READ_NUL = 1
 CIOA_GROW_ZERO = 1              # cio_write_dev_grow.h
 CIOA_TX_RECOMPUTE, CIOA_TX_ZERO = 256, 512      # cio_write_dev_tx.h
 CIOA_RELEASE_ZERO, CIOA_RELEASE_COMPACT = 1, 2  # cio_write_dev_pool.h
+CIOA_POOL_SET_MAX = 8           # cio_write_dev_pool_set.h
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -592,6 +593,115 @@ def rotate_pool_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec
         _ptr(total), _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_rotate_pool_records_batch_dev")
     return status[:n], total, out_offs, out_caps, out_img, out_count
+
+
+def pool_set_state(classes, stride, device):
+    """An empty pool set (cio_write_dev_pool_set.h).  classes: a list of 1 ..
+    CIOA_POOL_SET_MAX (cls, pal) pairs, cls strictly increasing; stride: the
+    entries each class's arrays hold, which is also its capacity.  Returns
+    (set_offs, set_caps, set, n_cls, stride): int64 cuda tensors of n_cls *
+    stride entries and of 4 * n_cls words [entries, capacity, cls, pal], and
+    the two host arguments."""
+    import torch
+    classes = [(int(c), int(p)) for c, p in classes]
+    n_cls, stride = len(classes), int(stride)
+    if not 1 <= n_cls <= CIOA_POOL_SET_MAX or stride < 1:
+        raise ValueError("a pool set has 1 .. 8 classes and a stride of at least 1")
+    offs = torch.zeros(n_cls * stride, dtype=torch.int64, device=device)
+    caps = torch.zeros(n_cls * stride, dtype=torch.int64, device=device)
+    words = torch.tensor([w for c, p in classes for w in (0, stride, c, p)], dtype=torch.int64, device=device)
+    return offs, caps, words, n_cls, stride
+
+
+def pool_set_class(set, k):
+    """Class k of a pool set as a pool of cio_write_dev_pool.h: the views
+    (pool_offs, pool_caps, pool) for release_batch_dev and the
+    rotate_pool_*_batch_dev calls.  set: what pool_set_state returns."""
+    offs, caps, words, n_cls, stride = set
+    if not 0 <= k < n_cls:
+        raise IndexError("no such class")
+    return offs[k * stride:(k + 1) * stride], caps[k * stride:(k + 1) * stride], words[4 * k:4 * k + 4]
+
+
+def _set_args(set):
+    from .crc32 import _ptr
+    offs, caps, words, n_cls, stride = set
+    return _ptr(offs), _ptr(caps), _ptr(words), int(n_cls), int(stride)
+
+
+def release_set_batch_dev(writer, base, offs, caps, set, img=None, count=None, gate=None, live_offs=None, flags=0,
+                          total=None, status=None, stream=None):
+    """release_batch_dev into a pool set (cio_file_release_set_batch_dev): every
+    releasable slot is filed into the largest class whose cls it reaches and
+    whose alignment its offset has, while that class has room; a cut entry is
+    kept and not offered to a lower class.  set: (set_offs, set_caps, set,
+    n_cls, stride) as from pool_set_state.  Returns (status int32, total
+    int64[2 + n_cls]) cuda tensors without waiting: total[0] the releasable
+    entries, total[1] the entries kept, total[2 + k] the releasable entries of
+    class k, whatever its room."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(offs.numel())
+    if img is not None and img.element_size() != 4:
+        raise ValueError("img must be a 32-bit tensor")
+    if total is None:
+        total = torch.zeros(2 + int(set[3]), dtype=torch.int64, device=base.device)
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_release_set_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(offs), _ptr(caps), _ptr(img), n, _ptr(count), _ptr(gate),
+        _ptr(live_offs), int(flags), *_set_args(set), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_release_set_batch_dev")
+    return status[:n], total
+
+
+def grow_set_batch_dev(writer, base, img_offs, img_caps, need, arena, set, realloc=32768, page=4096, align=16,
+                       flags=0, prev_offs=None, prev_caps=None, total=None, status=None, stream=None):
+    """grow_batch_dev that takes the larger slots from a pool set before it
+    touches the arena (cio_file_grow_set_batch_dev): an image that is to grow
+    asks the smallest usable class whose cls holds its new capacity, and gets
+    that class's top entry with the entry's whole capacity in img_caps[i];
+    when the class is empty it gets an arena slot of the class's size, and
+    without a class one of its new capacity.  set: (set_offs, set_caps, set,
+    n_cls, stride) as from pool_set_state, filled by release_set_batch_dev; the
+    classes' counts are lowered by the call.  Returns (status int32, total
+    int64[2 + n_cls]): total[0] the arena bytes all arena-bound images would
+    need, total[1] the pool entries consumed, total[2 + k] the images of class
+    k."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    if total is None:
+        total = torch.zeros(2 + int(set[3]), dtype=torch.int64, device=base.device)
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_grow_set_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(need), _ptr(arena),
+        *_set_args(set), int(realloc), int(page), int(align), int(flags), _ptr(prev_offs), _ptr(prev_caps),
+        _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_grow_set_batch_dev")
+    return status[:n], total
+
+
+def grow_set_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_lens, arena, set, realloc=32768,
+                               page=4096, align=16, flags=0, prev_offs=None, prev_caps=None, total=None, status=None,
+                               stream=None):
+    """grow_set_batch_dev ahead of write_records_batch_dev or its ungrouped form
+    (cio_file_grow_set_records_batch_dev): the needs are summed on the device
+    from the record list, as in grow_records_batch_dev.  An index >= n rejects
+    the whole call, and no set word changes."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n, n_rec = int(img_offs.numel()), int(rec_img.numel())
+    if rec_img.element_size() != 4:
+        raise ValueError("rec_img must be a 32-bit tensor")
+    if total is None:
+        total = torch.zeros(2 + int(set[3]), dtype=torch.int64, device=base.device)
+    status = _status_out(status, n, base.device)
+    rc = _lib.lib().cio_file_grow_set_records_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(rec_img),
+        _ptr(rec_lens), n_rec, _ptr(arena), *_set_args(set), int(realloc), int(page), int(align), int(flags),
+        _ptr(prev_offs), _ptr(prev_caps), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_grow_set_records_batch_dev")
+    return status[:n], total
 
 
 def tx_state(n, device):

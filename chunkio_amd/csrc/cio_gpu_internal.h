@@ -7,7 +7,7 @@
 // append; sort_records_gpu.hip: the ungrouped append's sort; grow_dev_gpu.hip:
 // growing images out of an arena; rotate_dev_gpu.hip: rotating full images;
 // tx_dev_gpu.hip: transactions on images; pool_dev_gpu.hip: recycling drained
-// slots through a pool;
+// slots through a pool; pool_set_gpu.hip: the size-classed set of such pools;
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
@@ -154,6 +154,37 @@ int rotate_check_args(const RotArgs &a, bool records);
 // otherwise), groom its ordinal in its workgroup, rtot the workgroups'
 // exclusive counts, seed the CRC states, and in a.total rotate's dev_total.
 int rotate_launch_front(const RotArgs &a, bool records, hipStream_t s);
+
+// The arguments of a grow call (grow_dev_gpu.hip; the calls that take the
+// larger slots from a pool set first, pool_set_gpu.hip, share them).
+struct GrowArgs {
+    const char *who;
+    cio_dev_writer *w;
+    void *dev_base;
+    uint64_t dev_bytes;
+    uint64_t *offs, *caps;
+    size_t n;
+    const uint64_t *need;                     // NULL: the records variant
+    const uint32_t *rec_img;
+    const uint64_t *rec_lens;
+    size_t n_rec;
+    uint64_t *arena;
+    uint64_t realloc_size, page, align;
+    int flags;
+    uint64_t *prev_offs, *prev_caps, *total;
+    int32_t *status;
+};
+
+// The argument checks of the grow calls, before any device call
+// (grow_dev_gpu.hip): 0 go on, 1 a no-op (an empty batch), CIO_ERROR refused.
+int grow_check_args(const GrowArgs &a, bool records);
+
+// The head of a grow batch, unchanged, for the set variant: grow_clear and
+// grow_need (records; a.need == NULL) and grow_headers.  Leaves the statuses of
+// rules 1..4, prev_*, and in the writer's arenas soff / slen the old offset and
+// the used bytes and gcap the reference's new capacity of an image that reaches
+// rule 4 (all 0 otherwise).
+int grow_launch_front(const GrowArgs &a, hipStream_t s);
 
 }  // namespace cioa
 

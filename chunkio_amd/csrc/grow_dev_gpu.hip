@@ -283,24 +283,6 @@ uint32_t blocks_of(size_t n, uint32_t per)
     return (uint32_t) ((n + per - 1) / per);
 }
 
-struct GrowArgs {
-    const char *who;
-    cio_dev_writer *w;
-    void *dev_base;
-    uint64_t dev_bytes;
-    uint64_t *offs, *caps;
-    size_t n;
-    const uint64_t *need;                     // NULL: the records variant
-    const uint32_t *rec_img;
-    const uint64_t *rec_lens;
-    size_t n_rec;
-    uint64_t *arena;
-    uint64_t realloc_size, page, align;
-    int flags;
-    uint64_t *prev_offs, *prev_caps, *total;
-    int32_t *status;
-};
-
 bool pow2(uint64_t v)
 {
     return v != 0 && (v & (v - 1)) == 0;
@@ -427,6 +409,34 @@ int launch_grow(const GrowArgs &a, hipStream_t s, const GrowEvents *ev)
 }
 
 }  // namespace
+
+int cioa::grow_check_args(const GrowArgs &a, bool records)
+{
+    return check_grow(a, records);
+}
+
+// The head of launch_grow for the variant that takes its slots from a pool set
+// first (pool_set_gpu.hip): the need kernels of the records variant and
+// grow_headers, as they are.
+int cioa::grow_launch_front(const GrowArgs &a, hipStream_t s)
+{
+    cio_dev_writer *w = a.w;
+    const uint32_t n = (uint32_t) a.n, nb = blocks_of(a.n, kGrowBlock);
+    const uint64_t *need = a.need;
+    if (!need) {
+        unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
+        hipLaunchKernelGGL(grow_clear, dim3(blocks_of(a.n, 256)), dim3(256), 0, s, acc, n, w->growhdr);
+        hipLaunchKernelGGL(grow_need, dim3(blocks_of(a.n_rec, 256)), dim3(256), 0, s, a.rec_img, a.rec_lens,
+                           (uint32_t) a.n_rec, n, acc, w->growhdr);
+        need = w->gneed;
+    }
+    hipLaunchKernelGGL(grow_headers, dim3(nb), dim3(kGrowBlock), 0, s, reinterpret_cast<uint8_t *>(a.dev_base),
+                       a.dev_bytes, a.offs, a.caps, n, need, a.need ? (const uint32_t *) nullptr : w->growhdr,
+                       a.arena, a.realloc_size, a.page, a.align, a.prev_offs, a.prev_caps, a.status, w->soff,
+                       w->slen, w->dst, w->gcap, w->rtot);
+    HIP_TRY(hipGetLastError(), "grow: front kernels launch");
+    return CIO_OK;
+}
 
 // One launch of grow_zero over the planner's image of (zoff, zlen): region i,
 // zlen[i] bytes at dev_base + zoff[i], becomes zero.  The rollback's fill as

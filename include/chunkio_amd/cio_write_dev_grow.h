@@ -79,9 +79,11 @@
  *
  * Not here: reusing freed slots -- cio_write_dev_pool.h releases the previous
  * slots (dev_prev_offs / dev_prev_caps with dev_live_offs = dev_img_offs) to a
- * device-side pool that the next rotation takes from; grow itself keeps
- * taking from the arena (and a packed CIOA_READ_IMAGE read into a fresh buffer
- * still compacts);
+ * device-side pool that the next rotation takes from, and
+ * cio_write_dev_pool_set.h has the grow that takes its larger slots from a
+ * size-classed set of such pools before the arena
+ * (cio_file_grow_set_batch_dev); the two calls here keep taking from the arena
+ * (and a packed CIOA_READ_IMAGE read into a fresh buffer still compacts);
  * extending in place an image that ends at top; growth for
  * cio_file_write_metadata_batch_dev (the caller passes the metadata delta as
  * the need and grows first); fusing the grow into the append kernels.

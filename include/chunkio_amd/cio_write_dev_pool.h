@@ -113,16 +113,18 @@
  * An entry that does not lie inside dev_bytes, or whose capacity is below cls,
  * makes the call write outside the buffer.
  *
- * GROW keeps taking from the arena: a single-class pool cannot serve its
- * per-image capacities without a second scan.  Its leftovers can be released:
- * pass cio_file_grow_batch_dev's dev_prev_offs / dev_prev_caps as dev_offs /
- * dev_caps with dev_live_offs = dev_img_offs; exactly the old slots of the
- * moved images enter the pool.
+ * GROW keeps taking from the arena in this header: a single-class pool cannot
+ * serve its per-image capacities without a second scan.  Its leftovers can be
+ * released: pass cio_file_grow_batch_dev's dev_prev_offs / dev_prev_caps as
+ * dev_offs / dev_caps with dev_live_offs = dev_img_offs; exactly the old slots
+ * of the moved images enter the pool.
  *
- * Not here: grow taking from the pool; more than one size class per pool (a
- * caller keeps several pools); coalescing adjacent free slots, and compaction
- * of live images; checking for duplicate entries within one release; a fused
- * verify + copy drain.
+ * Not here: grow taking from the pool, and more than one size class per pool
+ * -- both are cio_write_dev_pool_set.h's, whose set of K classes is K pools of
+ * this header side by side, so the calls here work on one class of it
+ * unchanged; coalescing adjacent free slots, and compaction of live images;
+ * checking for duplicate entries within one release; a fused verify + copy
+ * drain.
  */
 #ifndef CIO_WRITE_DEV_POOL_H
 #define CIO_WRITE_DEV_POOL_H
