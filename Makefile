@@ -19,7 +19,7 @@ HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -std=c++17 -Wall $(INC) -munsafe-fp
             -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-kernarg-preload-count=9
 
 COBJS   := $(BLD)/host_copy.o $(BLD)/crc32_host.o $(BLD)/crc32_scalar.o $(BLD)/cio_verify.o $(BLD)/cio_sync.o $(BLD)/cioa_chunk.o $(BLD)/crc_route.o $(BLD)/crc_cpu_batch.o $(BLD)/cio_sha1.o
-HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o
+HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o
 
 CTEST   := tests/c/bin
 REF_INC := /root/reference/include/chunkio/cio_crc32.h
@@ -89,13 +89,13 @@ ablib:
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/crc32_gpu_$(VAR).o $(SRC)/crc32_gpu.hip
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/gpu_runtime_$(VAR).o $(SRC)/gpu_runtime.hip
 	$(CXX) $(CXXFLAGS) $(DEFS) -c -o $(BLD)/ab/crc_plan_$(VAR).o $(SRC)/crc_plan.cpp
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/probe_gpu.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/probe_gpu.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o -lpthread
 
 # Same for the SHA-1 kernel: make ablib_sha1 VAR=name DEFS="-DCIO_SHA1_CHAINS=32"
 ablib_sha1:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/sha1_gpu_$(VAR).o $(SRC)/sha1_gpu.hip
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o -lpthread
 
 asm: $(BLD)/asm/crc32_gpu.s $(BLD)/asm/probe_gpu.s
 
@@ -203,6 +203,21 @@ poolsetcheck:
 	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/poolsetcheck/pool_set_check tools/pool_set_check.cpp
 	$(BLD)/poolsetcheck/pool_set_check
 
+# Coalescing the pool set's free slots (coalesce.h, the text the device kernels
+# run) under ASan + UBSan, stand-alone (no GPU, no HIP): the whole chain
+# workgroup by workgroup in three orders and wave by wave with the ballots
+# emulated over 64 lanes, the sort as sort_records.h's passes, against a
+# sequential loop in 128-bit arithmetic, the arrays being of exactly the set's
+# extent.
+coalescecheck:
+	@mkdir -p $(BLD)/coalescecheck
+	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/coalescecheck/coalesce_check tools/coalesce_check.cpp
+	$(BLD)/coalescecheck/coalesce_check
+
+# The device assembly of the units the coalescing touched or added, for a diff
+# against the parent's: make asmset.
+asmset: $(BLD)/asm/sort_records_gpu.s $(BLD)/asm/pool_set_gpu.s $(BLD)/asm/coalesce_gpu.s
+
 # make install PREFIX=/usr/local: the library, the public headers (crc32/crc32.h,
 # sha1/sha1.h, chunkio_amd/*.h) and a pkg-config file, for a chunkio build to
 # link against.
@@ -221,4 +236,4 @@ clean:
 	rm -rf $(BLD) $(LIB) $(CTEST)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck copycheck movecheck placecheck recordscheck sortcheck growcheck rotatecheck txcheck poolcheck poolsetcheck install
+.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck copycheck movecheck placecheck recordscheck sortcheck growcheck rotatecheck txcheck poolcheck poolsetcheck coalescecheck asmset install

@@ -30,6 +30,8 @@ Layers:
                                                    pool_set_state, pool_set_class,
                                                    release_set_batch_dev, grow_set_batch_dev /
                                                    grow_set_records_batch_dev;
+                                                   cio_write_dev_coalesce.h:
+                                                   coalesce_set_dev;
                                                    cio_write_dev_tx.h:
                                                    tx_state, tx_begin / tx_rollback /
                                                    tx_commit / tx_cond_records_batch_dev)
@@ -53,6 +55,7 @@ from .chunkfile import (  # noqa: F401,E402
     rotate_pool_records_batch_dev,
     CIOA_POOL_SET_MAX, grow_set_batch_dev, grow_set_records_batch_dev, pool_set_class, pool_set_state,
     release_set_batch_dev,
+    COALESCE_DRY, coalesce_set_dev,
     tx_begin_batch_dev, tx_commit_batch_dev, tx_cond_records_batch_dev, tx_rollback_batch_dev, tx_state,
     verify_batch_dev, write_at_batch_dev, write_batch_dev, write_metadata_batch_dev, write_records_batch_dev,
     write_records_ungrouped_batch_dev,

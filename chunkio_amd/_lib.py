@@ -57,6 +57,8 @@ EXPORTS = (
     "cio_file_release_batch_dev", "cio_file_rotate_pool_batch_dev", "cio_file_rotate_pool_records_batch_dev",
     # include/chunkio_amd/cio_write_dev_pool_set.h
     "cio_file_release_set_batch_dev", "cio_file_grow_set_batch_dev", "cio_file_grow_set_records_batch_dev",
+    # include/chunkio_amd/cio_write_dev_coalesce.h
+    "cio_file_coalesce_set_dev",
     # include/chunkio_amd/cio_write_dev_tx.h
     "cio_file_tx_begin_batch_dev", "cio_file_tx_rollback_batch_dev", "cio_file_tx_commit_batch_dev",
     "cio_file_tx_cond_records_batch_dev",
@@ -170,6 +172,8 @@ def _bind(lib):
                                                                ctypes.c_size_t, V, V, V, V, ctypes.c_size_t,
                                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                                ctypes.c_uint64, ctypes.c_int, V, V, V, V, V]),
+        "cio_file_coalesce_set_dev": (ctypes.c_int, [V, ctypes.c_uint64, V, V, V, ctypes.c_size_t, ctypes.c_uint64,
+                                                     ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, V, V]),
         "cio_file_tx_begin_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, ctypes.c_int, V, V,
                                                        V, V]),
         "cio_file_tx_rollback_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V,

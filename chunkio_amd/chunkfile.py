@@ -74,6 +74,7 @@ CIOA_GROW_ZERO = 1              # cio_write_dev_grow.h
 CIOA_TX_RECOMPUTE, CIOA_TX_ZERO = 256, 512      # cio_write_dev_tx.h
 CIOA_RELEASE_ZERO, CIOA_RELEASE_COMPACT = 1, 2  # cio_write_dev_pool.h
 CIOA_POOL_SET_MAX = 8           # cio_write_dev_pool_set.h
+COALESCE_DRY = 1                # cio_write_dev_coalesce.h: CIOA_COALESCE_DRY
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -702,6 +703,31 @@ def grow_set_records_batch_dev(writer, base, img_offs, img_caps, rec_img, rec_le
         _ptr(prev_offs), _ptr(prev_caps), _ptr(total), _ptr(status), _stream_ptr(stream))
     _lib.check(rc, "cio_file_grow_set_records_batch_dev")
     return status[:n], total
+
+
+def coalesce_set_dev(writer, dev_bytes, set, target, align=16, flags=0, total=None, stream=None):
+    """Coalesce the adjacent free slots of a pool set into slots of class
+    `target` on the device (cio_file_coalesce_set_dev), and drop its
+    ill-formed, duplicate and overlapping entries: the entries are sorted by
+    offset, runs of neighbouring slots below the target class become slots of
+    at least that class, and every class is rewritten in ascending offset --
+    all or nothing.  dev_bytes: the size of the buffer the slots lie in (no
+    byte of it is touched); set: (set_offs, set_caps, set, n_cls, stride) as
+    from pool_set_state; align: the alignment every slot of the buffer starts
+    on.  COALESCE_DRY computes the totals and changes nothing.  Returns total
+    int64[5 + n_cls] without waiting: total[0] 0 done, 1 the set is unsound, 2
+    a class would overflow (nothing changed); total[1] entries dropped as
+    ill-formed or classless, total[2] as duplicates or overlaps; total[3] the
+    groups formed, total[4] the entries they are made of; total[5 + k] the
+    entries of class k afterwards."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    if total is None:
+        total = torch.zeros(5 + int(set[3]), dtype=torch.int64, device=set[2].device)
+    rc = _lib.lib().cio_file_coalesce_set_dev(writer._handle, int(dev_bytes), *_set_args(set), int(target),
+                                              int(align), int(flags), _ptr(total), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_coalesce_set_dev")
+    return total
 
 
 def tx_state(n, device):

@@ -8,6 +8,7 @@
 // growing images out of an arena; rotate_dev_gpu.hip: rotating full images;
 // tx_dev_gpu.hip: transactions on images; pool_dev_gpu.hip: recycling drained
 // slots through a pool; pool_set_gpu.hip: the size-classed set of such pools;
+// coalesce_gpu.hip: coalescing that set's adjacent free slots;
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
@@ -185,6 +186,13 @@ int grow_check_args(const GrowArgs &a, bool records);
 // the used bytes and gcap the reference's new capacity of an image that reaches
 // rule 4 (all 0 otherwise).
 int grow_launch_front(const GrowArgs &a, hipStream_t s);
+
+// The ungrouped append's stable LSD radix sort (sort_records_gpu.hip), for the
+// coalescing of a pool set as well: (key, index) of n_rec records by key =
+// min(rec_img[r], n_img), sort_passes(n_img) passes between the writer's two
+// (skey, sidx) arena pairs, the histogram table in stab.  *sorted: the pair
+// that holds the result.  rec_img must be none of those arenas.
+int sort_launch(cio_dev_writer *w, const uint32_t *rec_img, size_t n_img, size_t n_rec, int *sorted, hipStream_t s);
 
 }  // namespace cioa
 

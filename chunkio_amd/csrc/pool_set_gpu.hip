@@ -57,13 +57,16 @@
 // in the sort's histogram table (stab), which neither chain uses otherwise:
 // kPoolSetMax + 17 64-bit words against the 128 it has per workgroup.  The
 // arithmetic is pool_set.h, the text tools/pool_set_check.cpp runs on the
-// host.  Plain C++ and vector stores throughout.
+// host; the workgroup scans (block_scan_excl, class_rank, class_scan,
+// totals_scan) are set_scan_gpu.h's, shared with coalesce_gpu.hip.  Plain C++
+// and vector stores throughout.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "cio_gpu_internal.h"
 #include "pool_set.h"
+#include "set_scan_gpu.h"
 #include "chunkio_amd/cio_write_dev_pool_set.h"
 
 using namespace cioa;
@@ -88,101 +91,6 @@ __device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes
     const uint64_t meta = ((uint32_t) p[22] << 8) | p[23];
     const uint64_t content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
     return kReadHdr + meta + content <= cap;
-}
-
-// Exclusive scan of v over the kSetBlock threads of a workgroup with
-// place_add, through LDS; total: the sum over the workgroup.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t *sh, uint32_t tid, uint64_t v, uint64_t &total)
-{
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < kSetBlock; off <<= 1) {
-        const uint64_t x = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] = place_add(x, sh[tid]);
-        __syncthreads();
-    }
-    const uint64_t excl = tid ? sh[tid - 1] : 0;
-    total = sh[kSetBlock - 1];
-    __syncthreads();
-    return excl;
-}
-
-// The K-way counting scan of one workgroup: every thread brings its class c
-// (kSetNone: none).  Returns the number of entries before the thread in its
-// workgroup with its class; tab gets the workgroup's count of every class.
-__device__ __forceinline__ uint32_t class_rank(uint32_t *wcount, uint32_t c, uint64_t *__restrict__ tab, uint32_t nb)
-{
-    const uint32_t tid = threadIdx.x, lane = tid & (kSetWave - 1), wave = tid / kSetWave;
-    const bool holds = c != kSetNone;
-    if (tid < kSetWaves * kPoolSetMax) {
-        wcount[tid] = 0;
-    }
-    uint64_t ballot[kSetBits];
-    const uint64_t all = __ballot(holds);
-    for (uint32_t bit = 0; bit < kSetBits; ++bit) {
-        ballot[bit] = __ballot(holds && ((c >> bit) & 1u));
-    }
-    const uint64_t match = set_match(all, ballot, c);
-    const uint32_t rank = sort_lane_rank(match, lane);
-    __syncthreads();
-    if (holds && rank == 0) {                 // the first lane of each class present in the wave
-        wcount[wave * kPoolSetMax + c] = sort_popcount(match);
-    }
-    __syncthreads();
-    if (tid < kPoolSetMax) {
-        tab[set_tab_at(tid, blockIdx.x, nb)] = set_wave_scan(wcount, tid);
-    }
-    __syncthreads();
-    return holds ? wcount[wave * kPoolSetMax + c] + rank : 0;
-}
-
-// tab[(k, j)] becomes the count of class k before workgroup j, for k < n_cls;
-// reach[k] (LDS) the class's total.  ONE workgroup.  As the sort scans its
-// histogram: one linear exclusive scan of the class-major table, whatever
-// n_cls is, then every word less its class's first (set_class_excl).  The
-// counts add up to at most n < 2^32: no sum wraps.
-__device__ __forceinline__ void class_scan(uint64_t *sh, uint64_t *reach, uint64_t *tab, uint32_t nb, uint32_t n_cls)
-{
-    __shared__ uint64_t first[kPoolSetMax];
-    const uint32_t tid = threadIdx.x, words = n_cls * nb;
-    uint64_t carry = 0;                       // the counts before `base` (the same in every thread)
-    for (uint32_t base = 0; base < words; base += kSetBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < words ? tab[j] : 0, pass);
-        if (j < words) {
-            tab[j] = carry + excl;
-        }
-        carry += pass;
-    }
-    __syncthreads();                          // the table's words, across the workgroup
-    if (tid < n_cls) {
-        first[tid] = tab[set_tab_at(tid, 0, nb)];
-        reach[tid] = set_class_total(first[tid], tid + 1 < n_cls ? tab[set_tab_at(tid + 1, 0, nb)] : carry);
-    }
-    __syncthreads();
-    for (uint32_t j = tid; j < words; j += kSetBlock) {
-        tab[j] = set_class_excl(tab[j], first[j / nb]);
-    }
-    __syncthreads();
-}
-
-// rtot[j] becomes the sum of the totals before workgroup j; returns their sum.
-__device__ __forceinline__ uint64_t totals_scan(uint64_t *sh, uint64_t *__restrict__ rtot, uint32_t nb)
-{
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kSetBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < nb ? rtot[j] : 0, pass);
-        if (j < nb) {
-            rtot[j] = place_add(carry, excl);
-        }
-        carry = place_add(carry, pass);
-    }
-    return carry;
 }
 
 // ---------------------------------------------------------------- release into the set

@@ -183,8 +183,13 @@ uint32_t blocks_of(size_t n, uint32_t per)
     return (uint32_t) ((n + per - 1) / per);
 }
 
+}  // namespace
+
 // The sort's passes; *sorted: the arena pair (0 or 1) that holds the result.
-int launch_sort(cio_dev_writer *w, const uint32_t *rec_img, size_t n_img, size_t n_rec, int *sorted, hipStream_t s)
+// Declared in cio_gpu_internal.h: coalesce_gpu.hip sorts a pool set's entries
+// by offset with it.
+int cioa::sort_launch(cio_dev_writer *w, const uint32_t *rec_img, size_t n_img, size_t n_rec, int *sorted,
+                      hipStream_t s)
 {
     const uint32_t nb = sort_blocks(n_rec), passes = sort_passes((uint32_t) n_img);
     int in = 1;                               // pass 0 reads rec_img; no arena
@@ -197,10 +202,12 @@ int launch_sort(cio_dev_writer *w, const uint32_t *rec_img, size_t n_img, size_t
                            (uint32_t) n_img, (uint32_t) n_rec, nb, w->stab, w->skey[out], w->sidx[out]);
         in = out;
     }
-    HIP_TRY(hipGetLastError(), "cio_file_write_records_ungrouped_batch_dev: sort kernels launch");
+    HIP_TRY(hipGetLastError(), "the device sort (ungrouped append, coalesce): sort kernels launch");
     *sorted = in;
     return CIO_OK;
 }
+
+namespace {
 
 int launch_gather(cio_dev_writer *w, int sorted, const uint64_t *rec_offs, const uint64_t *rec_lens, size_t n_rec,
                   uint32_t *order, hipStream_t s)
@@ -240,7 +247,7 @@ int cio_file_write_records_ungrouped_batch_dev(cio_dev_writer *w, void *dev_base
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int sorted = 0;
-    if (launch_sort(w, dev_rec_img, n_img, n_rec, &sorted, s) != CIO_OK ||
+    if (sort_launch(w, dev_rec_img, n_img, n_rec, &sorted, s) != CIO_OK ||
         launch_gather(w, sorted, dev_rec_offs, dev_rec_lens, n_rec, dev_rec_order, s) != CIO_OK ||
         cio_file_write_records_batch_dev(w, dev_base, dev_bytes, dev_img_offs, dev_img_caps, n_img, dev_src,
                                          src_bytes, w->gimg, w->goffs, w->glens, n_rec, flags, dev_crc_cur,
@@ -267,7 +274,7 @@ int cioa_debug_sort_records_events(cio_dev_writer *w, size_t n_img, const uint32
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int sorted = 0;
     HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_start), s), "hipEventRecord");
-    if (launch_sort(w, dev_rec_img, n_img, n_rec, &sorted, s) != CIO_OK ||
+    if (sort_launch(w, dev_rec_img, n_img, n_rec, &sorted, s) != CIO_OK ||
         launch_gather(w, sorted, dev_rec_offs, dev_rec_lens, n_rec, dev_rec_order, s) != CIO_OK ||
         launch_unpermute(w, sorted, n_rec, dev_rec_status, s) != CIO_OK) {
         return CIO_ERROR;

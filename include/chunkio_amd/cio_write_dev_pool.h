@@ -122,9 +122,9 @@
  * Not here: grow taking from the pool, and more than one size class per pool
  * -- both are cio_write_dev_pool_set.h's, whose set of K classes is K pools of
  * this header side by side, so the calls here work on one class of it
- * unchanged; coalescing adjacent free slots, and compaction of live images;
- * checking for duplicate entries within one release; a fused verify + copy
- * drain.
+ * unchanged; coalescing adjacent free slots and checking for duplicate entries
+ * within one release -- both are cio_write_dev_coalesce.h's, over a pool set;
+ * compaction of live images; a fused verify + copy drain.
  */
 #ifndef CIO_WRITE_DEV_POOL_H
 #define CIO_WRITE_DEV_POOL_H

@@ -121,9 +121,10 @@
  * output).
  *
  * Not here: spilling to the next class when one runs out (a cut entry of a
- * release is kept, an image whose class is empty goes to the arena);
- * coalescing adjacent free slots; checking for duplicate entries within one
- * release.
+ * release is kept, an image whose class is empty goes to the arena).
+ * Coalescing adjacent free slots of the set, and with it checking for
+ * duplicate entries within one release (the same sorted pass finds both), is
+ * cio_write_dev_coalesce.h's cio_file_coalesce_set_dev.
  */
 #ifndef CIO_WRITE_DEV_POOL_SET_H
 #define CIO_WRITE_DEV_POOL_SET_H
