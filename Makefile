@@ -84,139 +84,88 @@ oracle:
 # A/B variant of the library: make ablib VAR=name DEFS="-DFOO" -> chunkio_amd/lib/ab/name.so
 # $(DEFS) reaches every unit that reads cio_diag.h for CRC: the kernels, the
 # planner (CIO_HEAD_ALIGN in plan_build) and the runtime (cio_gpu_version).
+# Every other object is the shipped library's.
+ABOBJS  := crc32_gpu gpu_runtime crc_plan
 ablib:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/crc32_gpu_$(VAR).o $(SRC)/crc32_gpu.hip
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/gpu_runtime_$(VAR).o $(SRC)/gpu_runtime.hip
 	$(CXX) $(CXXFLAGS) $(DEFS) -c -o $(BLD)/ab/crc_plan_$(VAR).o $(SRC)/crc_plan.cpp
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/crc32_gpu_$(VAR).o $(BLD)/ab/gpu_runtime_$(VAR).o $(BLD)/ab/crc_plan_$(VAR).o $(BLD)/probe_gpu.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(ABOBJS:%=$(BLD)/ab/%_$(VAR).o) $(filter-out $(ABOBJS:%=$(BLD)/%.o),$(HOBJS)) -lpthread
 
 # Same for the SHA-1 kernel: make ablib_sha1 VAR=name DEFS="-DCIO_SHA1_CHAINS=32"
 ablib_sha1:
 	@mkdir -p $(OUT)/ab $(BLD)/ab
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o $(BLD)/ab/sha1_gpu_$(VAR).o $(SRC)/sha1_gpu.hip
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/ab/sha1_gpu_$(VAR).o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(OUT)/ab/$(VAR).so $(COBJS) $(BLD)/ab/sha1_gpu_$(VAR).o $(filter-out $(BLD)/sha1_gpu.o,$(HOBJS)) -lpthread
 
+# The device assembly, for a diff against the parent's: `make asmall` every
+# .hip unit, `make asm` the CRC kernels and the probes, `make asmset` the units
+# of the pool set's coalescing.
+asmall: $(patsubst $(SRC)/%.hip,$(BLD)/asm/%.s,$(wildcard $(SRC)/*.hip))
 asm: $(BLD)/asm/crc32_gpu.s $(BLD)/asm/probe_gpu.s
+asmset: $(BLD)/asm/sort_records_gpu.s $(BLD)/asm/pool_set_gpu.s $(BLD)/asm/coalesce_gpu.s
 
 $(BLD)/asm/%.s: $(SRC)/%.hip $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
 	@mkdir -p $(BLD)/asm
 	$(HIPCC) $(HIPFLAGS) --offload-device-only -S -o $@ $<
 
-# The host planner under ASan + UBSan, stand-alone (no GPU, no HIP): the
-# shipped choices over the geometries of tests/test_plan_choice.py.
-plancheck:
+# The host checks: the HIP-free headers under csrc/ -- the text the device
+# kernels run -- under ASan + UBSan, each from a stand-alone program (no GPU,
+# no HIP): `make <name>check` builds tools/<program>.cpp and runs it.
+#   plancheck      the host planner: the shipped choices over the geometries of
+#                  tests/test_plan_choice.py (with crc_plan.cpp and crc32_host.c)
+#   copycheck      write_dev_copy.h: the append copy's partition and unit arithmetic
+#   movecheck      write_dev_move.h: the in-place move's partition, save / shift
+#                  split and tiles, the segments of each kernel in three orders
+#   placecheck     read_dev_place.h: the read path's header, scan and place
+#                  kernels workgroup by workgroup in three orders, against a
+#                  sequential sum
+#   recordscheck   write_dev_records.h: the grouped append's segmented scan and
+#                  acceptance, in three orders, against a sequential loop per image
+#   sortcheck      sort_records.h: the stable radix sort's histogram, scan and
+#                  scatter in three orders and wave by wave with the ballot
+#                  emulated over 64 lanes, against std::stable_sort
+#   growcheck      grow_dev.h: the header, scan, place and commit kernels in three
+#                  orders against a sequential loop in 128-bit arithmetic, and the
+#                  zero fill lane by lane over buffers of exactly the batch's extent
+#   rotatecheck    rotate_dev.h: the same for rotate, and the sums' wave-level
+#                  pre-reduction lane by lane against a sequential sum
+#   txcheck        tx_dev.h: begin, rollback (plain and the chain's header and
+#                  commit steps) and commit in three orders over real image bytes
+#                  in buffers of exactly the batch's extent, against a sequential
+#                  loop, and the condition kernel wave by wave over 64 explicit
+#                  lanes with a count of the atomics issued
+#   poolcheck      pool_dev.h: the release's kernels and the pool-aware rotate's
+#                  place and commit in three orders against a sequential loop in
+#                  128-bit arithmetic, the arrays of exactly the batch's extent
+#   poolsetcheck   pool_set.h: the release into the set and the grow out of it in
+#                  three orders and wave by wave with the ballots emulated over 64
+#                  lanes, against a sequential loop in 128-bit arithmetic
+#   coalescecheck  coalesce.h: the whole chain in three orders and wave by wave,
+#                  the sort as sort_records.h's passes, against a sequential loop
+#                  in 128-bit arithmetic, the arrays of exactly the set's extent
+#   imagecheck     image_dev.h: the image check at every boundary of its rules
+#                  over buffers of exactly the image's extent, and with a null
+#                  base where no byte may be read
+SANFLAGS := -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined
+CHECKS   := plan copy move place records sort grow rotate tx pool pool_set coalesce image
+CHECKTGT := $(foreach c,$(CHECKS),$(subst _,,$(c))check)
+
+# plan_check links the planner and the host CRC it calls.
+plan_CHECK_LINK := $(SRC)/crc_plan.cpp $(BLD)/plancheck/crc32_host.o -lpthread
+$(BLD)/plancheck/crc32_host.o: $(SRC)/crc32_host.c $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
 	@mkdir -p $(BLD)/plancheck
-	$(CC) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=gnu11 $(INC) -c -o $(BLD)/plancheck/crc32_host.o $(SRC)/crc32_host.c
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/plancheck/plan_check tools/plan_check.cpp $(SRC)/crc_plan.cpp $(BLD)/plancheck/crc32_host.o -lpthread
-	$(BLD)/plancheck/plan_check
+	$(CC) $(SANFLAGS) -std=gnu11 $(INC) -c -o $@ $<
 
-# The append copy's partition and unit arithmetic (write_dev_copy.h, the text
-# the device kernel runs) under ASan + UBSan, stand-alone (no GPU, no HIP).
-copycheck:
-	@mkdir -p $(BLD)/copycheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/copycheck/copy_check tools/copy_check.cpp
-	$(BLD)/copycheck/copy_check
-
-# The in-place move's partition, save / shift split and tile arithmetic
-# (write_dev_move.h, the text the device kernels run) under ASan + UBSan,
-# stand-alone (no GPU, no HIP), the segments of each kernel in three orders.
-movecheck:
-	@mkdir -p $(BLD)/movecheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/movecheck/move_check tools/move_check.cpp
-	$(BLD)/movecheck/move_check
-
-# The read path's placement (read_dev_place.h, the text the device kernels run)
-# under ASan + UBSan, stand-alone (no GPU, no HIP): the header, scan and place
-# kernels workgroup by workgroup in three orders, against a sequential sum.
-placecheck:
-	@mkdir -p $(BLD)/placecheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/placecheck/place_check tools/place_check.cpp
-	$(BLD)/placecheck/place_check
-
-# The grouped append's segmented scan and acceptance (write_dev_records.h, the
-# text the device kernels run) under ASan + UBSan, stand-alone (no GPU, no
-# HIP): the record, scan and place kernels workgroup by workgroup in three
-# orders, against a sequential loop per image.
-recordscheck:
-	@mkdir -p $(BLD)/recordscheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/recordscheck/records_check tools/records_check.cpp
-	$(BLD)/recordscheck/records_check
-
-# The ungrouped append's stable radix sort (sort_records.h, the text the device
-# kernels run) under ASan + UBSan, stand-alone (no GPU, no HIP): the histogram,
-# scan and scatter kernels workgroup by workgroup in three orders and wave by
-# wave with the ballot emulated over 64 lanes, against std::stable_sort.
-sortcheck:
-	@mkdir -p $(BLD)/sortcheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/sortcheck/sort_check tools/sort_check.cpp
-	$(BLD)/sortcheck/sort_check
-
-# Growing images out of an arena (grow_dev.h, the text the device kernels run)
-# under ASan + UBSan, stand-alone (no GPU, no HIP): the header, scan, place and
-# commit kernels workgroup by workgroup in three orders against a sequential
-# loop in 128-bit arithmetic, and the zero fill lane by lane over buffers of
-# exactly the batch's extent.
-growcheck:
-	@mkdir -p $(BLD)/growcheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/growcheck/grow_check tools/grow_check.cpp
-	$(BLD)/growcheck/grow_check
-
-# Rotating full images (rotate_dev.h, the text the device kernels run) under
-# ASan + UBSan, stand-alone (no GPU, no HIP): the header, scan, place and
-# commit kernels workgroup by workgroup in three orders against a sequential
-# loop in 128-bit arithmetic, and the sums' wave-level pre-reduction lane by
-# lane against a sequential sum.
-rotatecheck:
-	@mkdir -p $(BLD)/rotatecheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/rotatecheck/rotate_check tools/rotate_check.cpp
-	$(BLD)/rotatecheck/rotate_check
-
-# Transactions on images (tx_dev.h, the text the device kernels run) under ASan
-# + UBSan, stand-alone (no GPU, no HIP): begin, rollback (plain and the chain's
-# header and commit steps) and commit workgroup by workgroup in three orders
-# over real image bytes in buffers of exactly the batch's extent, against a
-# sequential loop, and the condition kernel wave by wave over 64 explicit lanes
-# with a count of the atomics issued.
-txcheck:
-	@mkdir -p $(BLD)/txcheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/txcheck/tx_check tools/tx_check.cpp
-	$(BLD)/txcheck/tx_check
-
-# Recycling drained slots (pool_dev.h, the text the device kernels run) under
-# ASan + UBSan, stand-alone (no GPU, no HIP): the release's header, scan, place
-# and commit kernels and the pool-aware rotate's place and commit workgroup by
-# workgroup in three orders against a sequential loop in 128-bit arithmetic,
-# the arrays being of exactly the batch's extent.
-poolcheck:
-	@mkdir -p $(BLD)/poolcheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/poolcheck/pool_check tools/pool_check.cpp
-	$(BLD)/poolcheck/pool_check
-
-# The size-classed pool set (pool_set.h, the text the device kernels run) under
-# ASan + UBSan, stand-alone (no GPU, no HIP): the release into the set and the
-# grow out of it workgroup by workgroup in three orders and wave by wave with
-# the ballots emulated over 64 lanes, against a sequential loop in 128-bit
-# arithmetic, the arrays being of exactly the batch's extent.
-poolsetcheck:
-	@mkdir -p $(BLD)/poolsetcheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/poolsetcheck/pool_set_check tools/pool_set_check.cpp
-	$(BLD)/poolsetcheck/pool_set_check
-
-# Coalescing the pool set's free slots (coalesce.h, the text the device kernels
-# run) under ASan + UBSan, stand-alone (no GPU, no HIP): the whole chain
-# workgroup by workgroup in three orders and wave by wave with the ballots
-# emulated over 64 lanes, the sort as sort_records.h's passes, against a
-# sequential loop in 128-bit arithmetic, the arrays being of exactly the set's
-# extent.
-coalescecheck:
-	@mkdir -p $(BLD)/coalescecheck
-	$(CXX) -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/coalescecheck/coalesce_check tools/coalesce_check.cpp
-	$(BLD)/coalescecheck/coalesce_check
-
-# The device assembly of the units the coalescing touched or added, for a diff
-# against the parent's: make asmset.
-asmset: $(BLD)/asm/sort_records_gpu.s $(BLD)/asm/pool_set_gpu.s $(BLD)/asm/coalesce_gpu.s
+# $(1): the program's name without _check, $(2): the target
+define CHECK_RULE
+$(2): $$(filter %.o,$$($(1)_CHECK_LINK))
+	@mkdir -p $(BLD)/$(2)
+	$(CXX) $(SANFLAGS) -Wall -Wextra -std=c++17 $(INC) -o $(BLD)/$(2)/$(1)_check tools/$(1)_check.cpp $$($(1)_CHECK_LINK)
+	$(BLD)/$(2)/$(1)_check
+endef
+$(foreach c,$(CHECKS),$(eval $(call CHECK_RULE,$(c),$(subst _,,$(c))check)))
 
 # make install PREFIX=/usr/local: the library, the public headers (crc32/crc32.h,
 # sha1/sha1.h, chunkio_amd/*.h) and a pkg-config file, for a chunkio build to
@@ -236,4 +185,4 @@ clean:
 	rm -rf $(BLD) $(LIB) $(CTEST)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle asm clean ctests ablib ablib_sha1 plancheck copycheck movecheck placecheck recordscheck sortcheck growcheck rotatecheck txcheck poolcheck poolsetcheck coalescecheck asmset install
+.PHONY: all oracle asm asmall asmset clean ctests ablib ablib_sha1 $(CHECKTGT) install

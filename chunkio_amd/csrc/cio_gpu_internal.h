@@ -12,7 +12,13 @@
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
-// planner of crc_plan.cpp -- is in cio_plan.h.  Not installed.
+// planner of crc_plan.cpp -- is in cio_plan.h.  What the units of the chunk
+// images share on the device is in two headers of its own: image_dev.h, the
+// image check (no HIP type: the host checks run it too), and block_scan_gpu.h,
+// the workgroup scan and the scan of the workgroup totals (set_scan_gpu.h adds
+// the class-counting scans of the pool set).  What they share on the host is
+// here: blocks_of, pow2, fail_who, SectionEvents / mark, and the launchers one
+// unit exports to the others.  Not installed.
 #ifndef CIOA_GPU_INTERNAL_H
 #define CIOA_GPU_INTERNAL_H
 
@@ -31,6 +37,8 @@ constexpr int kMaxDev = 64;          // device ordinals with per-device state
 extern thread_local std::string g_err;
 // Record the message for cio_gpu_last_error(); returns CIO_ERROR.
 int fail(const char *what, hipError_t e = hipSuccess);
+// The same for an argument check's message under the caller's name: "who: what".
+int fail_who(const char *who, const char *what);
 // The calling thread's current device's state (built on first use).
 int device_state(DeviceState **out);
 // One launch of plan p over dev_base (chunk-id map cid: outputs and seeds by id).
@@ -46,6 +54,26 @@ int devplan_launch_planner(const cio_crc32_devplan *dp, uint64_t dev_bytes, cons
 // S and ntiny from the device header hdr (crc32_gpu.hip).
 int devplan_crc_launch(const cio_crc32_plan *p, const unsigned long long *hdr, const void *dev_base,
                        const uint32_t *dev_seeds, uint32_t *dev_out, size_t n, hipStream_t s);
+
+// Workgroups of `per` entries that cover n.
+inline uint32_t blocks_of(size_t n, uint32_t per)
+{
+    return (uint32_t) ((n + per - 1) / per);
+}
+
+inline bool pow2(uint64_t v)
+{
+    return v != 0 && (v & (v - 1)) == 0;
+}
+
+// Measurement (the cioa_debug_*_events hooks): the two events go around ONE
+// section of a launch chain.  mark() records ev0 (begin) or ev1 on s where
+// `section` is the chosen one, and nothing where ev is NULL.
+struct SectionEvents {
+    int section;
+    hipEvent_t ev0, ev1;
+};
+int mark(const SectionEvents *ev, int section, bool begin, hipStream_t s);
 
 }  // namespace cioa
 
@@ -114,6 +142,13 @@ int launch_copy(const cio_dev_writer *w, void *dev_dst, const void *dev_src, siz
 int launch_zero_fill(const cio_dev_writer *w, void *dev_base, const uint64_t *zoff, const uint64_t *zlen, size_t n,
                      hipStream_t s);
 
+// The records-to-need sums of the grow and rotate calls' records variants
+// (grow_clear and grow_need, grow_dev_gpu.hip): w->gneed[i] becomes the sum of
+// min(rec_lens[r], 2^32) over the records of image i, and w->growhdr[0] whether
+// an index lies outside the n_img images.  n_rec == 0: the clear alone.
+int launch_need_sums(const cio_dev_writer *w, const uint32_t *rec_img, const uint64_t *rec_lens, size_t n_img,
+                     size_t n_rec, hipStream_t s);
+
 // The argument checks of cio_file_write_records_batch_dev and of the ungrouped
 // call that runs it behind a sort (write_records_gpu.hip): 0 go on, 1 a no-op
 // (an empty batch), CIO_ERROR refused, the message under the name `who`.
@@ -149,12 +184,13 @@ struct RotArgs {
 // (rotate_dev_gpu.hip): 0 go on, 1 a no-op (an empty batch), CIO_ERROR refused.
 int rotate_check_args(const RotArgs &a, bool records);
 
-// The head of a rotate batch, unchanged, for the pool variant: rotate_clear and
-// rotate_sums (records), rotate_headers and rotate_scan.  Leaves in the
-// writer's arenas gcap = 24 + meta of an image that reaches the placement (0
-// otherwise), groom its ordinal in its workgroup, rtot the workgroups'
-// exclusive counts, seed the CRC states, and in a.total rotate's dev_total.
-int rotate_launch_front(const RotArgs &a, bool records, hipStream_t s);
+// The head of a rotate batch, for the pool variant as well: the need sums
+// (records), rotate_headers and rotate_scan.  Leaves in the writer's arenas
+// gcap = 24 + meta of an image that reaches the placement (0 otherwise), groom
+// its ordinal in its workgroup, rtot the workgroups' exclusive counts, seed the
+// CRC states, and in a.total rotate's dev_total.  ev: the hook's marks around
+// the sums, and the one that opens the bookkeeping (the caller closes it).
+int rotate_launch_front(const RotArgs &a, bool records, hipStream_t s, const SectionEvents *ev = nullptr);
 
 // The arguments of a grow call (grow_dev_gpu.hip; the calls that take the
 // larger slots from a pool set first, pool_set_gpu.hip, share them).
@@ -180,12 +216,13 @@ struct GrowArgs {
 // (grow_dev_gpu.hip): 0 go on, 1 a no-op (an empty batch), CIO_ERROR refused.
 int grow_check_args(const GrowArgs &a, bool records);
 
-// The head of a grow batch, unchanged, for the set variant: grow_clear and
-// grow_need (records; a.need == NULL) and grow_headers.  Leaves the statuses of
-// rules 1..4, prev_*, and in the writer's arenas soff / slen the old offset and
-// the used bytes and gcap the reference's new capacity of an image that reaches
-// rule 4 (all 0 otherwise).
-int grow_launch_front(const GrowArgs &a, hipStream_t s);
+// The head of a grow batch, for the set variant as well: the need sums
+// (records; a.need == NULL) and grow_headers.  Leaves the statuses of rules
+// 1..4, prev_*, and in the writer's arenas soff / slen the old offset and the
+// used bytes and gcap the reference's new capacity of an image that reaches
+// rule 4 (all 0 otherwise).  ev: the hook's marks around the sums, and the one
+// that opens the bookkeeping (the caller closes it).
+int grow_launch_front(const GrowArgs &a, hipStream_t s, const SectionEvents *ev = nullptr);
 
 // The ungrouped append's stable LSD radix sort (sort_records_gpu.hip), for the
 // coalescing of a pool set as well: (key, index) of n_rec records by key =

@@ -354,11 +354,6 @@ coal_commit(const uint64_t *__restrict__ words, const uint64_t *__restrict__ sof
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 struct CoalArgs {
     cio_dev_writer *w;
     uint64_t dev_bytes;

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "cio_gpu_internal.h"
+#include "image_dev.h"
 #include "chunkio_amd/cio_verify.h"
 
 using namespace cioa;
@@ -371,11 +372,6 @@ plan_waves(uint32_t n, uint32_t W, const ChunkDesc *__restrict__ desc,
 }
 
 // ---------------------------------------------------------------- verify-on-load
-
-__device__ __forceinline__ uint32_t be32(const uint8_t *p)
-{
-    return ((uint32_t) p[0] << 24) | ((uint32_t) p[1] << 16) | ((uint32_t) p[2] << 8) | p[3];
-}
 
 // cio_verify.c's per-chunk header checks (taint 0, read-only map), one image
 // per thread.  Emits the CRC region [img + 22, + 2 + meta_len + content_len);

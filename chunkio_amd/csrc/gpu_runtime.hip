@@ -36,6 +36,20 @@ int fail(const char *what, hipError_t e)
     return CIO_ERROR;
 }
 
+int fail_who(const char *who, const char *what)
+{
+    const std::string msg = std::string(who) + ": " + what;
+    return fail(msg.c_str());
+}
+
+int mark(const SectionEvents *ev, int section, bool begin, hipStream_t s)
+{
+    if (ev && ev->section == section) {
+        HIP_TRY(hipEventRecord(begin ? ev->ev0 : ev->ev1, s), "hipEventRecord");
+    }
+    return CIO_OK;
+}
+
 }  // namespace cioa
 
 extern "C" int cioa_fail_msg(const char *what, const char *detail)

@@ -45,6 +45,7 @@
 
 #include "cio_gpu_internal.h"
 #include "grow_dev.h"
+#include "block_scan_gpu.h"
 #include "chunkio_amd/cio_write_dev_grow.h"
 
 using namespace cioa;
@@ -53,45 +54,6 @@ namespace {
 
 constexpr uint32_t kZeroThreads = 256;                 // 4 waves per workgroup, the copy kernel's shape
 constexpr uint32_t kZeroWaves = kZeroThreads / kWave;
-
-__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The write path's image check (image_ok in write_dev_gpu.hip), restated.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap,
-                                         uint32_t &meta, uint64_t &content)
-{
-    if (!range_ok(off, cap, dev_bytes) || cap < kReadHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    meta = ((uint32_t) p[22] << 8) | p[23];
-    content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kReadHdr + meta + content <= cap;
-}
-
-// Exclusive scan of v over the kGrowBlock threads of a workgroup with
-// place_add, through LDS; total: the sum over the workgroup.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t *sh, uint32_t tid, uint64_t v, uint64_t &total)
-{
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < kGrowBlock; off <<= 1) {
-        const uint64_t x = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] = place_add(x, sh[tid]);
-        __syncthreads();
-    }
-    const uint64_t excl = tid ? sh[tid - 1] : 0;
-    total = sh[kGrowBlock - 1];
-    __syncthreads();
-    return excl;
-}
 
 __global__ void __launch_bounds__(256)
 grow_clear(unsigned long long *__restrict__ need, uint32_t n, uint32_t *__restrict__ ghdr)
@@ -181,18 +143,11 @@ grow_scan(uint64_t *__restrict__ rtot, uint32_t nb, const uint64_t *__restrict__
           uint64_t *__restrict__ total)
 {
     __shared__ uint64_t sh[kGrowBlock];
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;                       // the totals before `base` (the same in every thread)
-    for (uint32_t base = 0; base < nb; base += kGrowBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < nb ? rtot[j] : 0, pass);
-        if (j < nb) {
-            rtot[j] = place_add(carry, excl);
-        }
-        carry = place_add(carry, pass);
+    uint64_t carry = 0;                       // totals_scan, written out (block_scan_gpu.h)
+    for (uint32_t base = 0; base < nb; base += kScanBlock) {
+        carry = totals_pass(sh, rtot, nb, base, carry);
     }
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         total[0] = grow_total(arena[0], align, carry);
     }
 }
@@ -278,103 +233,54 @@ grow_commit(uint64_t *__restrict__ img_offs, uint64_t *__restrict__ img_caps, ui
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
-bool pow2(uint64_t v)
-{
-    return v != 0 && (v & (v - 1)) == 0;
-}
-
 // The argument checks, before any device call.  Returns 1 when the call is a
 // no-op (an empty batch), 0 to go on, CIO_ERROR.
 int check_grow(const GrowArgs &a, bool records)
 {
-    std::string msg;
     if (a.flags & ~CIOA_GROW_ZERO) {
-        msg = std::string(a.who) + ": unknown flags";
-        return fail(msg.c_str());
+        return fail_who(a.who, "unknown flags");
     }
     if (a.realloc_size == 0) {
-        msg = std::string(a.who) + ": realloc_size must not be 0";
-        return fail(msg.c_str());
+        return fail_who(a.who, "realloc_size must not be 0");
     }
     if (!pow2(a.page)) {
-        msg = std::string(a.who) + ": page must be a power of two";
-        return fail(msg.c_str());
+        return fail_who(a.who, "page must be a power of two");
     }
     if (!pow2(a.align) || a.align > 4096) {
-        msg = std::string(a.who) + ": align must be a power of two in 1 .. 4096";
-        return fail(msg.c_str());
+        return fail_who(a.who, "align must be a power of two in 1 .. 4096");
     }
     if ((a.prev_offs == nullptr) != (a.prev_caps == nullptr)) {
-        msg = std::string(a.who) + ": dev_prev_offs and dev_prev_caps go together";
-        return fail(msg.c_str());
+        return fail_who(a.who, "dev_prev_offs and dev_prev_caps go together");
     }
     if (!a.w) {
-        msg = std::string(a.who) + ": null writer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null writer");
     }
     if (a.n == 0 || (records && a.n_rec == 0)) {
         return 1;
     }
     if (!a.dev_base || !a.offs || !a.caps || !a.arena || !a.total || !a.status ||
         (records ? !a.rec_img || !a.rec_lens : !a.need)) {
-        msg = std::string(a.who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null pointer");
     }
     if (a.n > a.w->max_chunks) {
-        msg = std::string(a.who) + ": more images than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(a.who, "more images than the writer was created for");
     }
     if (records && a.n_rec > a.w->max_chunks) {
-        msg = std::string(a.who) + ": more records than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(a.who, "more records than the writer was created for");
     }
     return 0;
 }
 
-// Measurement: the two events go around one section of the chain.
+// Measurement: the sections of cioa_debug_grow_events (SectionEvents).
 enum { kSecNone = 0, kSecNeed, kSecBook, kSecCopy, kSecZero, kSecCommit };
 
-struct GrowEvents {
-    int section;
-    hipEvent_t ev0, ev1;
-};
-
-int mark(const GrowEvents *ev, int section, bool begin, hipStream_t s)
-{
-    if (ev && ev->section == section) {
-        HIP_TRY(hipEventRecord(begin ? ev->ev0 : ev->ev1, s), "hipEventRecord");
-    }
-    return CIO_OK;
-}
-
-int launch_grow(const GrowArgs &a, hipStream_t s, const GrowEvents *ev)
+int launch_grow(const GrowArgs &a, hipStream_t s, const SectionEvents *ev)
 {
     cio_dev_writer *w = a.w;
-    uint8_t *base = reinterpret_cast<uint8_t *>(a.dev_base);
     const uint32_t n = (uint32_t) a.n, nb = blocks_of(a.n, kGrowBlock);
-    const uint64_t *need = a.need;
-    if (mark(ev, kSecNeed, true, s) != CIO_OK) {
+    if (grow_launch_front(a, s, ev) != CIO_OK) {
         return CIO_ERROR;
     }
-    if (!need) {
-        unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
-        hipLaunchKernelGGL(grow_clear, dim3(blocks_of(a.n, 256)), dim3(256), 0, s, acc, n, w->growhdr);
-        hipLaunchKernelGGL(grow_need, dim3(blocks_of(a.n_rec, 256)), dim3(256), 0, s, a.rec_img, a.rec_lens,
-                           (uint32_t) a.n_rec, n, acc, w->growhdr);
-        HIP_TRY(hipGetLastError(), "grow: need kernels launch");
-        need = w->gneed;
-    }
-    if (mark(ev, kSecNeed, false, s) != CIO_OK || mark(ev, kSecBook, true, s) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    hipLaunchKernelGGL(grow_headers, dim3(nb), dim3(kGrowBlock), 0, s, base, a.dev_bytes, a.offs, a.caps, n, need,
-                       a.need ? (const uint32_t *) nullptr : w->growhdr, a.arena, a.realloc_size, a.page, a.align,
-                       a.prev_offs, a.prev_caps, a.status, w->soff, w->slen, w->dst, w->gcap, w->rtot);
     hipLaunchKernelGGL(grow_scan, dim3(1), dim3(kGrowBlock), 0, s, w->rtot, nb, a.arena, a.align, a.total);
     hipLaunchKernelGGL(grow_place, dim3(nb), dim3(kGrowBlock), 0, s, n, w->rtot, a.arena, a.dev_bytes, a.align,
                        a.status, w->soff, w->slen, w->dst, w->gcap, w->roff, w->rlen, w->newlen);
@@ -415,20 +321,41 @@ int cioa::grow_check_args(const GrowArgs &a, bool records)
     return check_grow(a, records);
 }
 
-// The head of launch_grow for the variant that takes its slots from a pool set
-// first (pool_set_gpu.hip): the need kernels of the records variant and
-// grow_headers, as they are.
-int cioa::grow_launch_front(const GrowArgs &a, hipStream_t s)
+// grow_clear and, where there are records, grow_need: the records-to-need sums
+// of the grow calls and of the rotate calls (rotate_dev_gpu.hip).
+int cioa::launch_need_sums(const cio_dev_writer *w, const uint32_t *rec_img, const uint64_t *rec_lens, size_t n_img,
+                           size_t n_rec, hipStream_t s)
+{
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
+    hipLaunchKernelGGL(grow_clear, dim3(blocks_of(n_img, 256)), dim3(256), 0, s, acc, (uint32_t) n_img, w->growhdr);
+    if (n_rec != 0) {
+        hipLaunchKernelGGL(grow_need, dim3(blocks_of(n_rec, 256)), dim3(256), 0, s, rec_img, rec_lens,
+                           (uint32_t) n_rec, (uint32_t) n_img, acc, w->growhdr);
+    }
+    HIP_TRY(hipGetLastError(), "need sums kernels launch");
+    return CIO_OK;
+}
+
+// The head of launch_grow, and of the variant that takes its slots from a pool
+// set first (pool_set_gpu.hip): the need sums of the records variant and
+// grow_headers.  No event lies between grow_headers and grow_scan, so the
+// bookkeeping section opens here and closes in the caller.
+int cioa::grow_launch_front(const GrowArgs &a, hipStream_t s, const SectionEvents *ev)
 {
     cio_dev_writer *w = a.w;
     const uint32_t n = (uint32_t) a.n, nb = blocks_of(a.n, kGrowBlock);
     const uint64_t *need = a.need;
+    if (mark(ev, kSecNeed, true, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
     if (!need) {
-        unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
-        hipLaunchKernelGGL(grow_clear, dim3(blocks_of(a.n, 256)), dim3(256), 0, s, acc, n, w->growhdr);
-        hipLaunchKernelGGL(grow_need, dim3(blocks_of(a.n_rec, 256)), dim3(256), 0, s, a.rec_img, a.rec_lens,
-                           (uint32_t) a.n_rec, n, acc, w->growhdr);
+        if (launch_need_sums(w, a.rec_img, a.rec_lens, a.n, a.n_rec, s) != CIO_OK) {
+            return CIO_ERROR;
+        }
         need = w->gneed;
+    }
+    if (mark(ev, kSecNeed, false, s) != CIO_OK || mark(ev, kSecBook, true, s) != CIO_OK) {
+        return CIO_ERROR;
     }
     hipLaunchKernelGGL(grow_headers, dim3(nb), dim3(kGrowBlock), 0, s, reinterpret_cast<uint8_t *>(a.dev_base),
                        a.dev_bytes, a.offs, a.caps, n, need, a.need ? (const uint32_t *) nullptr : w->growhdr,
@@ -505,7 +432,7 @@ int cioa_debug_grow_events(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes
         (section == kSecZero && !(flags & CIOA_GROW_ZERO)) || check_grow(a, dev_need == nullptr) != 0) {
         return fail("cioa_debug_grow_events: bad argument");
     }
-    const GrowEvents ev = {section, reinterpret_cast<hipEvent_t>(ev_start), reinterpret_cast<hipEvent_t>(ev_stop)};
+    const SectionEvents ev = {section, reinterpret_cast<hipEvent_t>(ev_start), reinterpret_cast<hipEvent_t>(ev_stop)};
     return launch_grow(a, reinterpret_cast<hipStream_t>(stream), &ev);
 }
 

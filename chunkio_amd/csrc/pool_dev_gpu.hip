@@ -27,7 +27,7 @@
 //                    planner's status
 //
 // A rotate batch from the pool is rotate's chain with its own place and commit:
-// rotate_clear, rotate_sums, rotate_headers and rotate_scan run unchanged
+// the need sums, rotate_headers and rotate_scan run unchanged
 // (rotate_launch_front, rotate_dev_gpu.hip); rotpool_place gives ordinal j <
 // F pool entry count - 1 - j and every later ordinal arena slot j - F, and
 // rewrites dev_total[0]; the planner, append_copy and the CRC launch follow as
@@ -43,49 +43,12 @@
 
 #include "cio_gpu_internal.h"
 #include "pool_dev.h"
+#include "block_scan_gpu.h"
 #include "chunkio_amd/cio_write_dev_pool.h"
 
 using namespace cioa;
 
 namespace {
-
-__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The write path's image check (image_ok in write_dev_gpu.hip), restated.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap)
-{
-    if (!range_ok(off, cap, dev_bytes) || cap < kReadHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    const uint64_t meta = ((uint32_t) p[22] << 8) | p[23];
-    const uint64_t content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kReadHdr + meta + content <= cap;
-}
-
-// Exclusive scan of v over the kPoolBlock threads of a workgroup with
-// place_add, through LDS; total: the sum over the workgroup.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t *sh, uint32_t tid, uint64_t v, uint64_t &total)
-{
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < kPoolBlock; off <<= 1) {
-        const uint64_t x = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] = place_add(x, sh[tid]);
-        __syncthreads();
-    }
-    const uint64_t excl = tid ? sh[tid - 1] : 0;
-    total = sh[kPoolBlock - 1];
-    __syncthreads();
-    return excl;
-}
 
 // code[i] takes kRelIn and kRelReach, ord[i] the number of entries before i in
 // its workgroup that reach the placement, rtot[blockIdx.x] the workgroup's
@@ -113,8 +76,10 @@ release_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restr
         } else {
             const uint64_t cap = caps[i];
             const uint64_t cls = pool[kPoolCls], pal = pool[kPoolAlign];
-            if (pool_sound(pool[kPoolCount], pool[kPoolCap], cls, pal) && image_ok(base, dev_bytes, off, cap) &&
-                pool_takes(off, cap, cls, pal)) {
+            uint32_t meta;                        // the image's lengths: checked, not used
+            uint64_t content;
+            if (pool_sound(pool[kPoolCount], pool[kPoolCap], cls, pal) &&
+                image_ok(base, dev_bytes, off, cap, meta, content) && pool_takes(off, cap, cls, pal)) {
                 c |= kRelReach;
             } else {
                 st = CIO_ERROR;
@@ -140,18 +105,11 @@ release_scan(uint64_t *__restrict__ rtot, uint32_t nb, uint32_t n, const uint64_
              const uint64_t *__restrict__ pool, uint64_t *__restrict__ total)
 {
     __shared__ uint64_t sh[kPoolBlock];
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;                       // the counts before `base` (the same in every thread)
-    for (uint32_t base = 0; base < nb; base += kPoolBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < nb ? rtot[j] : 0, pass);
-        if (j < nb) {
-            rtot[j] = place_add(carry, excl);
-        }
-        carry = place_add(carry, pass);
+    uint64_t carry = 0;                       // totals_scan, written out (block_scan_gpu.h)
+    for (uint32_t base = 0; base < nb; base += kScanBlock) {
+        carry = totals_pass(sh, rtot, nb, base, carry);
     }
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         const uint64_t m = pool_m(n, count != nullptr, count ? count[0] : 0);
         total[0] = carry;
         total[1] = pool_kept_total(m, carry,
@@ -379,11 +337,6 @@ rotpool_commit(uint8_t *base, uint64_t *__restrict__ img_offs, uint64_t *__restr
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 struct RelArgs {
     cio_dev_writer *w;
     void *dev_base;
@@ -494,8 +447,7 @@ int rotate_pool(const RotArgs &a, bool records, uint64_t *pool_offs, uint64_t *p
         return rc > 0 ? CIO_OK : rc;
     }
     if (!pool_offs || !pool_caps || !pool) {
-        const std::string msg = std::string(a.who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null pointer");
     }
     return launch_rotate_pool(a, records, pool_offs, pool_caps, pool, reinterpret_cast<hipStream_t>(stream));
 }

@@ -57,9 +57,9 @@
 // in the sort's histogram table (stab), which neither chain uses otherwise:
 // kPoolSetMax + 17 64-bit words against the 128 it has per workgroup.  The
 // arithmetic is pool_set.h, the text tools/pool_set_check.cpp runs on the
-// host; the workgroup scans (block_scan_excl, class_rank, class_scan,
-// totals_scan) are set_scan_gpu.h's, shared with coalesce_gpu.hip.  Plain C++
-// and vector stores throughout.
+// host; the workgroup scans are block_scan_gpu.h's (block_scan_excl,
+// totals_scan) and set_scan_gpu.h's (class_rank, class_scan), the latter
+// shared with coalesce_gpu.hip.  Plain C++ and vector stores throughout.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,26 +72,6 @@
 using namespace cioa;
 
 namespace {
-
-__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The write path's image check (image_ok in write_dev_gpu.hip), restated.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap)
-{
-    if (!range_ok(off, cap, dev_bytes) || cap < kReadHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    const uint64_t meta = ((uint32_t) p[22] << 8) | p[23];
-    const uint64_t content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kReadHdr + meta + content <= cap;
-}
 
 // ---------------------------------------------------------------- release into the set
 
@@ -118,7 +98,9 @@ relset_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restri
             st = CIO_ERROR;                       // the slot is not read
         } else {
             const uint64_t cap = caps[i];
-            if (set_sound(set, n_cls, stride) && image_ok(base, dev_bytes, off, cap)) {
+            uint32_t meta;                        // the image's lengths: checked, not used
+            uint64_t content;
+            if (set_sound(set, n_cls, stride) && image_ok(base, dev_bytes, off, cap, meta, content)) {
                 cls = set_release_class(set, n_cls, off, cap);
             }
             if (cls != kSetNone) {
@@ -494,11 +476,6 @@ growset_commit(uint64_t *__restrict__ img_offs, uint64_t *__restrict__ img_caps,
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 struct SetArgs {
     uint64_t *offs, *caps, *words;
     size_t n_cls;
@@ -509,14 +486,11 @@ struct SetArgs {
 // pointers where the call checks its own.
 int check_set_values(const char *who, const SetArgs &t)
 {
-    std::string msg;
     if (t.n_cls < 1 || t.n_cls > CIOA_POOL_SET_MAX) {
-        msg = std::string(who) + ": n_cls must be in 1 .. 8";
-        return fail(msg.c_str());
+        return fail_who(who, "n_cls must be in 1 .. 8");
     }
     if (t.stride == 0) {
-        msg = std::string(who) + ": stride must not be 0";
-        return fail(msg.c_str());
+        return fail_who(who, "stride must not be 0");
     }
     return 0;
 }
@@ -655,8 +629,7 @@ int grow_set(const GrowArgs &a, bool records, const SetArgs &t, void *stream)
         return rc > 0 ? CIO_OK : rc;
     }
     if (!t.offs || !t.caps || !t.words) {
-        const std::string msg = std::string(a.who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null pointer");
     }
     return launch_grow_set(a, t, reinterpret_cast<hipStream_t>(stream));
 }

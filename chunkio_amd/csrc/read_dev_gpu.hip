@@ -40,6 +40,7 @@
 
 #include "cio_gpu_internal.h"
 #include "read_dev_place.h"
+#include "block_scan_gpu.h"
 #include "write_dev_copy.h"
 #include "chunkio_amd/cio_read_dev.h"
 
@@ -49,47 +50,6 @@ namespace {
 
 constexpr uint32_t kCmpThreads = 256;                  // 4 waves, one image each
 constexpr uint32_t kCmpWaves = kCmpThreads / kWave;
-
-__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The write path's image check (image_ok in write_dev_gpu.hip), restated: the
-// image inside dev_bytes, room for a header, the magic, and metadata +
-// content inside the capacity.  No legacy length inference, no CRC.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap,
-                                         uint32_t &meta, uint64_t &content)
-{
-    if (!range_ok(off, cap, dev_bytes) || cap < kReadHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    meta = ((uint32_t) p[22] << 8) | p[23];
-    content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kReadHdr + meta + content <= cap;
-}
-
-// Exclusive scan of v over the kReadBlock threads of a workgroup with
-// place_add, through LDS; total: the sum over the workgroup.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t *sh, uint32_t tid, uint64_t v, uint64_t &total)
-{
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < kReadBlock; off <<= 1) {
-        const uint64_t x = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] = place_add(x, sh[tid]);
-        __syncthreads();
-    }
-    const uint64_t excl = tid ? sh[tid - 1] : 0;
-    total = sh[kReadBlock - 1];
-    __syncthreads();
-    return excl;
-}
 
 // PACKED: dst[i] takes the exclusive sum of the slots before entry i in its
 // workgroup and rtot[blockIdx.x] the workgroup's total.  Placed: dst[i] is
@@ -145,18 +105,11 @@ __global__ void __launch_bounds__(kReadBlock)
 read_scan(uint64_t *__restrict__ rtot, uint32_t nb, uint64_t *__restrict__ total)
 {
     __shared__ uint64_t sh[kReadBlock];
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;                       // the totals before `base` (the same in every thread)
-    for (uint32_t base = 0; base < nb; base += kReadBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < nb ? rtot[j] : 0, pass);
-        if (j < nb) {
-            rtot[j] = place_add(carry, excl);
-        }
-        carry = place_add(carry, pass);
+    uint64_t carry = 0;                       // totals_scan, written out (block_scan_gpu.h)
+    for (uint32_t base = 0; base < nb; base += kScanBlock) {
+        carry = totals_pass(sh, rtot, nb, base, carry);
     }
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         total[0] = carry;
     }
 }
@@ -235,11 +188,6 @@ meta_cmp(const uint8_t *__restrict__ base, uint64_t dev_bytes, const uint64_t *_
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 struct ReadArgs {
     const char *who;
     cio_dev_writer *w;
@@ -260,29 +208,23 @@ struct ReadArgs {
 // Returns 1 when the call is a no-op (n == 0), 0 to go on, CIO_ERROR.
 int check_read(const ReadArgs &a, bool pointers_ok)
 {
-    std::string msg;
     if (a.what != CIOA_READ_META && a.what != CIOA_READ_CONTENT && a.what != CIOA_READ_IMAGE) {
-        msg = std::string(a.who) + ": unknown what";
-        return fail(msg.c_str());
+        return fail_who(a.who, "unknown what");
     }
     if (a.flags & ~CIOA_READ_NUL) {
-        msg = std::string(a.who) + ": unknown flags";
-        return fail(msg.c_str());
+        return fail_who(a.who, "unknown flags");
     }
     if (!a.w) {
-        msg = std::string(a.who) + ": null writer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null writer");
     }
     if (a.n == 0) {
         return 1;
     }
     if (!a.dev_base || !a.offs || !a.caps || !a.out_lens || !a.status || !pointers_ok) {
-        msg = std::string(a.who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null pointer");
     }
     if (a.n > a.w->max_chunks) {
-        msg = std::string(a.who) + ": more images than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(a.who, "more images than the writer was created for");
     }
     return 0;
 }

@@ -9,17 +9,12 @@
 
 #include <stdint.h>
 
-#ifdef __HIPCC__
-#define CIOA_PLACE_FN __device__ __forceinline__
-#else
-#define CIOA_PLACE_FN inline
-#endif
+#include "image_dev.h"
 
 namespace cioa {
 
 constexpr uint32_t kReadBlock = 1024;       // images per workgroup of the header and place kernels
 constexpr uint64_t kPlaceOver = ~0ull;      // a sum that left 64 bits (or reached 2^64 - 1)
-constexpr uint64_t kReadHdr = 24;
 constexpr int kReadMeta = 0, kReadContent = 1, kReadImage = 2;   // CIOA_READ_* (cio_read_dev.h)
 
 // Record `what` of an image with meta bytes of metadata and content bytes of

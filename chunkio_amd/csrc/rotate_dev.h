@@ -1,6 +1,6 @@
 // rotate_dev.h -- the arithmetic of rotating full chunk images in HBM
-// (rotate_dev_gpu.hip: rotate_sums, rotate_headers, rotate_scan, rotate_place,
-// rotate_commit): whether an image is full, the slot of a fresh image and how
+// (rotate_dev_gpu.hip: rotate_sums_wave, rotate_headers, rotate_scan,
+// rotate_place, rotate_commit): whether an image is full, the slot of a fresh image and how
 // many of them the arena and the list of finished chunks still take, who writes
 // the arena's top and the list's count, the fresh image's 24 header bytes, the
 // CRC state after its two length bytes, and the wave-level pre-reduction of the

@@ -5,14 +5,15 @@
 //
 // A rotate batch is a serial chain of kernels on the caller's stream:
 //
-//   rotate_clear    records variant; one thread per image: the per-image need
-//                   arena and the header word re-zeroed (a kernel of its own:
-//                   zeroing inside rotate_sums would race with the sums of
-//                   other workgroups)
-//   rotate_sums     one thread per record: the index check (an index >= n_img is
-//                   published in the header word) and need[img] += min(len,
-//                   2^32), a plain atomicAdd.  (rotate_sums_wave, the same with
-//                   a wave-level pre-reduction -- a segmented scan over the wave
+//   grow_clear      records variant; grow's need sums (launch_need_sums,
+//   grow_need       grow_dev_gpu.hip), unchanged: the per-image need arena and
+//                   the header word re-zeroed (a kernel of its own: zeroing
+//                   inside the sums would race with the sums of other
+//                   workgroups), then one thread per record: the index check (an
+//                   index >= n_img is published in the header word) and
+//                   need[img] += min(len, 2^32), a plain atomicAdd.
+//                   (rotate_sums_wave, the same sums with a wave-level
+//                   pre-reduction -- a segmented scan over the wave
 //                   sums every run of equal indices, the last lane of a run
 //                   issues ONE atomicAdd -- is measured through the hook and not
 //                   launched by the calls: DESIGN.md §19.)
@@ -58,84 +59,17 @@
 
 #include "cio_gpu_internal.h"
 #include "rotate_dev.h"
+#include "block_scan_gpu.h"
 #include "chunkio_amd/cio_write_dev_rotate.h"
 
 using namespace cioa;
 
 namespace {
 
-__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The write path's image check (image_ok in write_dev_gpu.hip), restated.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap,
-                                         uint32_t &meta, uint64_t &content)
-{
-    if (!range_ok(off, cap, dev_bytes) || cap < kReadHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    meta = ((uint32_t) p[22] << 8) | p[23];
-    content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kReadHdr + meta + content <= cap;
-}
-
-// Exclusive scan of v over the kRotBlock threads of a workgroup with
-// place_add, through LDS; total: the sum over the workgroup.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t *sh, uint32_t tid, uint64_t v, uint64_t &total)
-{
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < kRotBlock; off <<= 1) {
-        const uint64_t x = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] = place_add(x, sh[tid]);
-        __syncthreads();
-    }
-    const uint64_t excl = tid ? sh[tid - 1] : 0;
-    total = sh[kRotBlock - 1];
-    __syncthreads();
-    return excl;
-}
-
-__global__ void __launch_bounds__(256)
-rotate_clear(unsigned long long *__restrict__ need, uint32_t n, uint32_t *__restrict__ ghdr)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) {
-        need[i] = 0;
-    }
-    if (i == 0) {
-        ghdr[0] = 0;
-    }
-}
-
-// The sums the calls run: one plain atomicAdd per record, as grow_need.  The
-// pre-reduction below missed one of the two conditions set for it (DESIGN.md
-// §19, leg (e)), so it is not what ships.
-__global__ void __launch_bounds__(kRotSumBlock)
-rotate_sums(const uint32_t *__restrict__ rec_img, const uint64_t *__restrict__ rec_lens, uint32_t n_rec,
-            uint32_t n_img, unsigned long long *need, uint32_t *ghdr)
-{
-    const uint32_t r = blockIdx.x * kRotSumBlock + threadIdx.x;
-    if (r >= n_rec) {
-        return;
-    }
-    const uint32_t img = rec_img[r];
-    if (img >= n_img) {
-        atomicOr(ghdr, 1u);                   // the whole call is rejected
-        return;
-    }
-    atomicAdd(need + img, (unsigned long long) umin(rec_lens[r], kGrowLenClamp));
-}
-
-// The same sums with a wave-level pre-reduction; launched by the measurement
-// hook only (section 6).  Every lane of every wave takes part in the shuffles:
+// The need sums (grow_need, grow_dev_gpu.hip: one plain atomicAdd per record)
+// with a wave-level pre-reduction; launched by the measurement hook only
+// (section 6).  It missed one of the two conditions set for it (DESIGN.md §19,
+// leg (e)), so it is not what ships.  Every lane of every wave takes part in the shuffles:
 // a lane without a record holds the key kRotNoImage and the length 0, and
 // never issues.
 __global__ void __launch_bounds__(kRotSumBlock)
@@ -226,18 +160,11 @@ rotate_scan(uint64_t *__restrict__ rtot, uint32_t nb, const uint64_t *__restrict
             uint64_t align, uint64_t *__restrict__ total)
 {
     __shared__ uint64_t sh[kRotBlock];
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;                       // the counts before `base` (the same in every thread)
-    for (uint32_t base = 0; base < nb; base += kRotBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < nb ? rtot[j] : 0, pass);
-        if (j < nb) {
-            rtot[j] = place_add(carry, excl);
-        }
-        carry = place_add(carry, pass);
+    uint64_t carry = 0;                       // totals_scan, written out (block_scan_gpu.h)
+    for (uint32_t base = 0; base < nb; base += kScanBlock) {
+        carry = totals_pass(sh, rtot, nb, base, carry);
     }
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         total[0] = rot_total(arena[0], align, carry, grow_round_up(new_cap, align));
         total[1] = carry;
     }
@@ -333,36 +260,21 @@ rotate_commit(uint8_t *base, uint64_t *__restrict__ img_offs, uint64_t *__restri
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
-bool pow2(uint64_t v)
-{
-    return v != 0 && (v & (v - 1)) == 0;
-}
-
 // The argument checks, before any device call.  Returns 1 when the call is a
 // no-op (an empty batch), 0 to go on, CIO_ERROR.
 int check_rotate(const RotArgs &a, bool records)
 {
-    std::string msg;
     if (a.flags & ~CIO_CHECKSUM) {
-        msg = std::string(a.who) + ": unknown flags";
-        return fail(msg.c_str());
+        return fail_who(a.who, "unknown flags");
     }
     if (a.new_cap < kReadHdr) {
-        msg = std::string(a.who) + ": new_cap must be at least 24";
-        return fail(msg.c_str());
+        return fail_who(a.who, "new_cap must be at least 24");
     }
     if (!pow2(a.align) || a.align > 4096) {
-        msg = std::string(a.who) + ": align must be a power of two in 1 .. 4096";
-        return fail(msg.c_str());
+        return fail_who(a.who, "align must be a power of two in 1 .. 4096");
     }
     if (!a.w) {
-        msg = std::string(a.who) + ": null writer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null writer");
     }
     if (a.n == 0 || (records && a.n_rec == 0)) {
         return 1;
@@ -370,71 +282,31 @@ int check_rotate(const RotArgs &a, bool records)
     if (!a.dev_base || !a.offs || !a.caps || !a.arena || !a.out_offs || !a.out_caps || !a.out_img ||
         !a.out_count || !a.total || !a.status || ((a.flags & CIO_CHECKSUM) && !a.crc_cur) ||
         (records && (!a.rec_img || !a.rec_lens))) {
-        msg = std::string(a.who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null pointer");
     }
     if (a.n > a.w->max_chunks) {
-        msg = std::string(a.who) + ": more images than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(a.who, "more images than the writer was created for");
     }
     if (records && a.n_rec > a.w->max_chunks) {
-        msg = std::string(a.who) + ": more records than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(a.who, "more records than the writer was created for");
     }
     return 0;
 }
 
-// Measurement: the two events go around one section of the chain.
+// Measurement: the sections of cioa_debug_rotate_events (SectionEvents).
 enum { kSecNone = 0, kSecSums, kSecBook, kSecCopy, kSecCrc, kSecCommit, kSecSumsWave };
 
-struct RotEvents {
-    int section;
-    hipEvent_t ev0, ev1;
-};
-
-int mark(const RotEvents *ev, int section, bool begin, hipStream_t s)
-{
-    if (ev && ev->section == section) {
-        HIP_TRY(hipEventRecord(begin ? ev->ev0 : ev->ev1, s), "hipEventRecord");
-    }
-    return CIO_OK;
-}
-
-int launch_rotate(const RotArgs &a, bool records, hipStream_t s, const RotEvents *ev)
+int launch_rotate(const RotArgs &a, bool records, hipStream_t s, const SectionEvents *ev)
 {
     cio_dev_writer *w = a.w;
     uint8_t *base = reinterpret_cast<uint8_t *>(a.dev_base);
     const uint32_t n = (uint32_t) a.n, nb = blocks_of(a.n, kRotBlock);
     const bool checksum = (a.flags & CIO_CHECKSUM) != 0;
-    const uint64_t *need = a.need;
-    const bool wave = ev && ev->section == kSecSumsWave;
-    if (mark(ev, kSecSums, true, s) != CIO_OK || mark(ev, kSecSumsWave, true, s) != CIO_OK) {
-        return CIO_ERROR;
-    }
-    if (records) {
-        unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
-        hipLaunchKernelGGL(rotate_clear, dim3(blocks_of(a.n, 256)), dim3(256), 0, s, acc, n, w->growhdr);
-        if (wave) {
-            hipLaunchKernelGGL(rotate_sums_wave, dim3(blocks_of(a.n_rec, kRotSumBlock)), dim3(kRotSumBlock), 0, s,
-                               a.rec_img, a.rec_lens, (uint32_t) a.n_rec, n, acc, w->growhdr);
-        } else {
-            hipLaunchKernelGGL(rotate_sums, dim3(blocks_of(a.n_rec, kRotSumBlock)), dim3(kRotSumBlock), 0, s,
-                               a.rec_img, a.rec_lens, (uint32_t) a.n_rec, n, acc, w->growhdr);
-        }
-        HIP_TRY(hipGetLastError(), "rotate: sums kernels launch");
-        need = w->gneed;
-    }
-    if (mark(ev, kSecSums, false, s) != CIO_OK || mark(ev, kSecSumsWave, false, s) != CIO_OK ||
-        mark(ev, kSecBook, true, s) != CIO_OK) {
+    if (rotate_launch_front(a, records, s, ev) != CIO_OK) {
         return CIO_ERROR;
     }
     // writer arenas: gcap 24 + meta of an image that reaches the placement, groom its ordinal, roff / rlen its
     // place and list index, newlen the place kernel's code
-    hipLaunchKernelGGL(rotate_headers, dim3(nb), dim3(kRotBlock), 0, s, base, a.dev_bytes, a.offs, a.caps, n, need,
-                       records ? w->growhdr : (const uint32_t *) nullptr, a.arena, a.limit, a.new_cap, a.status,
-                       w->gcap, w->groom, w->seed, w->rtot);
-    hipLaunchKernelGGL(rotate_scan, dim3(1), dim3(kRotBlock), 0, s, w->rtot, nb, a.arena, a.new_cap, a.align,
-                       a.total);
     hipLaunchKernelGGL(rotate_place, dim3(nb), dim3(kRotBlock), 0, s, n, w->rtot, a.arena, a.out_count, a.dev_bytes,
                        a.new_cap, a.align, a.offs, a.status, w->gcap, w->groom, w->soff, w->slen, w->dst, w->roff,
                        w->rlen, w->newlen);
@@ -470,19 +342,35 @@ int cioa::rotate_check_args(const RotArgs &a, bool records)
     return check_rotate(a, records);
 }
 
-// launch_rotate up to rotate_scan, without the measurement marks.
-int cioa::rotate_launch_front(const RotArgs &a, bool records, hipStream_t s)
+// The head of launch_rotate, and of the variant that takes its slots from a
+// pool first (pool_dev_gpu.hip): the need sums of the records variant,
+// rotate_headers and rotate_scan.  No event lies between rotate_scan and
+// rotate_place, so the bookkeeping section opens here and closes in the caller.
+int cioa::rotate_launch_front(const RotArgs &a, bool records, hipStream_t s, const SectionEvents *ev)
 {
     cio_dev_writer *w = a.w;
     const uint32_t n = (uint32_t) a.n, nb = blocks_of(a.n, kRotBlock);
     const uint64_t *need = a.need;
+    const bool wave = ev && ev->section == kSecSumsWave;
+    if (mark(ev, kSecSums, true, s) != CIO_OK || mark(ev, kSecSumsWave, true, s) != CIO_OK) {
+        return CIO_ERROR;
+    }
     if (records) {
-        unsigned long long *acc = reinterpret_cast<unsigned long long *>(w->gneed);
-        hipLaunchKernelGGL(rotate_clear, dim3(blocks_of(a.n, 256)), dim3(256), 0, s, acc, n, w->growhdr);
-        hipLaunchKernelGGL(rotate_sums, dim3(blocks_of(a.n_rec, kRotSumBlock)), dim3(kRotSumBlock), 0, s, a.rec_img,
-                           a.rec_lens, (uint32_t) a.n_rec, n, acc, w->growhdr);
-        HIP_TRY(hipGetLastError(), "rotate: sums kernels launch");
+        // section 6: the clear alone, then the pre-reduced sums in grow_need's place
+        if (launch_need_sums(w, a.rec_img, a.rec_lens, a.n, wave ? 0 : a.n_rec, s) != CIO_OK) {
+            return CIO_ERROR;
+        }
+        if (wave) {
+            hipLaunchKernelGGL(rotate_sums_wave, dim3(blocks_of(a.n_rec, kRotSumBlock)), dim3(kRotSumBlock), 0, s,
+                               a.rec_img, a.rec_lens, (uint32_t) a.n_rec, n,
+                               reinterpret_cast<unsigned long long *>(w->gneed), w->growhdr);
+            HIP_TRY(hipGetLastError(), "rotate: sums kernels launch");
+        }
         need = w->gneed;
+    }
+    if (mark(ev, kSecSums, false, s) != CIO_OK || mark(ev, kSecSumsWave, false, s) != CIO_OK ||
+        mark(ev, kSecBook, true, s) != CIO_OK) {
+        return CIO_ERROR;
     }
     hipLaunchKernelGGL(rotate_headers, dim3(nb), dim3(kRotBlock), 0, s, reinterpret_cast<const uint8_t *>(a.dev_base),
                        a.dev_bytes, a.offs, a.caps, n, need, records ? w->growhdr : (const uint32_t *) nullptr,
@@ -534,10 +422,10 @@ int cio_file_rotate_records_batch_dev(cio_dev_writer *w, void *dev_base, uint64_
 
 /* Measurement hook (not in the public header; tools/rotate_dev_ab.py): a whole
  * rotate call -- the records variant when dev_rec_img is not NULL -- with the
- * two HIP events around ONE section of its chain: 1 rotate_clear + rotate_sums,
+ * two HIP events around ONE section of its chain: 1 grow_clear + grow_need,
  * 2 rotate_headers + rotate_scan + rotate_place, 3 the planner and append_copy,
- * 4 the CRC launch, 5 rotate_commit, 6 rotate_clear + rotate_sums_wave (the
- * pre-reduced sums INSTEAD of rotate_sums; nothing else launches that kernel). */
+ * 4 the CRC launch, 5 rotate_commit, 6 grow_clear + rotate_sums_wave (the
+ * pre-reduced sums INSTEAD of grow_need; nothing else launches that kernel). */
 int cioa_debug_rotate_events(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes, uint64_t *dev_img_offs,
                              uint64_t *dev_img_caps, size_t n, const uint64_t *dev_need,
                              const uint32_t *dev_rec_img, const uint64_t *dev_rec_lens, size_t n_rec,
@@ -555,7 +443,7 @@ int cioa_debug_rotate_events(cio_dev_writer *w, void *dev_base, uint64_t dev_byt
         (section == kSecCrc && !(flags & CIO_CHECKSUM)) || check_rotate(a, records) != 0) {
         return fail("cioa_debug_rotate_events: bad argument");
     }
-    const RotEvents ev = {section, reinterpret_cast<hipEvent_t>(ev_start), reinterpret_cast<hipEvent_t>(ev_stop)};
+    const SectionEvents ev = {section, reinterpret_cast<hipEvent_t>(ev_start), reinterpret_cast<hipEvent_t>(ev_stop)};
     return launch_rotate(a, records, reinterpret_cast<hipStream_t>(stream), &ev);
 }
 

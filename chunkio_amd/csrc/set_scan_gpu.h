@@ -1,9 +1,9 @@
 // set_scan_gpu.h -- the workgroup scans the kernels of the pool set
-// (pool_set_gpu.hip) and of its coalescing (coalesce_gpu.hip) share: the
-// exclusive scan of one value per thread through LDS, the K-WAY COUNTING SCAN
-// of a class index per thread (three ballots, a [wave][class] table in LDS, the
+// (pool_set_gpu.hip) and of its coalescing (coalesce_gpu.hip) share beside
+// block_scan_gpu.h's (which this header includes): the K-WAY COUNTING SCAN of
+// a class index per thread (three ballots, a [wave][class] table in LDS, the
 // workgroup's K totals into the class-major table), and the single-workgroup
-// scans of that table and of a column of workgroup totals.  Device code: it
+// scan of that table.  Device code: it
 // needs HIP, unlike pool_set.h, whose arithmetic it calls.  In an unnamed
 // namespace, as it was inside pool_set_gpu.hip: every unit inlines its own
 // copy, and that unit's device code is what it was.  Not installed.
@@ -14,28 +14,11 @@
 #include <stdint.h>
 
 #include "pool_set.h"
+#include "block_scan_gpu.h"
 
 namespace {
 
 using namespace cioa;
-
-// Exclusive scan of v over the kSetBlock threads of a workgroup with
-// place_add, through LDS; total: the sum over the workgroup.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t *sh, uint32_t tid, uint64_t v, uint64_t &total)
-{
-    sh[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < kSetBlock; off <<= 1) {
-        const uint64_t x = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] = place_add(x, sh[tid]);
-        __syncthreads();
-    }
-    const uint64_t excl = tid ? sh[tid - 1] : 0;
-    total = sh[kSetBlock - 1];
-    __syncthreads();
-    return excl;
-}
 
 // The K-way counting scan of one workgroup: every thread brings its class c
 // (kSetNone: none).  Returns the number of entries before the thread in its
@@ -95,23 +78,6 @@ __device__ __forceinline__ void class_scan(uint64_t *sh, uint64_t *reach, uint64
         tab[j] = set_class_excl(tab[j], first[j / nb]);
     }
     __syncthreads();
-}
-
-// rtot[j] becomes the sum of the totals before workgroup j; returns their sum.
-__device__ __forceinline__ uint64_t totals_scan(uint64_t *sh, uint64_t *__restrict__ rtot, uint32_t nb)
-{
-    const uint32_t tid = threadIdx.x;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kSetBlock) {
-        const uint32_t j = base + tid;
-        uint64_t pass;
-        const uint64_t excl = block_scan_excl(sh, tid, j < nb ? rtot[j] : 0, pass);
-        if (j < nb) {
-            rtot[j] = place_add(carry, excl);
-        }
-        carry = place_add(carry, pass);
-    }
-    return carry;
 }
 
 }  // namespace

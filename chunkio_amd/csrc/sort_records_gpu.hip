@@ -178,11 +178,6 @@ sort_unpermute(const uint32_t *__restrict__ idx, const int32_t *__restrict__ gst
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 }  // namespace
 
 // The sort's passes; *sorted: the arena pair (0 or 1) that holds the result.

@@ -2,8 +2,8 @@
 // (tx_dev_gpu.hip: tx_begin, tx_rollback, tx_rollback_headers,
 // tx_rollback_commit, tx_commit, tx_cond_clear, tx_cond_records, tx_cond_apply,
 // tx_cond_last): what one thread of each kernel does for its image or its
-// record, given plain pointers -- the 16-byte state entry, the image check of
-// the write path, the order of the rollback's rules, the regions the chain
+// record, given plain pointers -- the 16-byte state entry, the image check
+// (image_dev.h), the order of the rollback's rules, the regions the chain
 // hands to the zero fill and to the CRC launch, the header bytes of a rollback
 // and of a commit, and which lane of a wave publishes a failing record.  No HIP
 // type, so that the same text compiles for the device and, stand-alone on the
@@ -48,36 +48,6 @@ CIOA_PLACE_FN void tx_store(TxState *p, uint32_t active, uint32_t content_len, u
     *reinterpret_cast<u32x4 *>(p) = v;
 }
 
-CIOA_PLACE_FN bool tx_range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The write path's image check (image_ok in write_dev_gpu.hip), restated.  No
-// byte is read unless [off, off + cap) lies inside dev_bytes and cap >= 24.
-CIOA_PLACE_FN bool tx_image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap, uint32_t &meta,
-                               uint64_t &content)
-{
-    if (!tx_range_ok(off, cap, dev_bytes) || cap < kReadHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    meta = ((uint32_t) p[22] << 8) | p[23];
-    content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kReadHdr + meta + content <= cap;
-}
-
-CIOA_PLACE_FN void tx_put_be32(uint8_t *p, uint32_t v)
-{
-    p[0] = (uint8_t) (v >> 24);
-    p[1] = (uint8_t) (v >> 16);
-    p[2] = (uint8_t) (v >> 8);
-    p[3] = (uint8_t) v;
-}
-
 // Is entry i acted on by a call whose condition selects `want_ok` entries?
 // Commit acts where cond is NULL or CIO_OK, rollback where it is NULL or not
 // CIO_OK: with the same array every entry is acted on by exactly one of them.
@@ -99,7 +69,7 @@ CIOA_PLACE_FN int32_t tx_begin_one(const uint8_t *base, uint64_t dev_bytes, cons
     }
     uint32_t meta = 0;
     uint64_t content = 0;
-    if (!tx_image_ok(base, dev_bytes, offs[i], caps[i], meta, content)) {
+    if (!image_ok(base, dev_bytes, offs[i], caps[i], meta, content)) {
         return kTxError;
     }
     tx_store(tx + i, 1, (uint32_t) content, crc_cur ? crc_cur[i] : 0, meta);
@@ -117,7 +87,7 @@ CIOA_PLACE_FN uint32_t tx_rollback_decide(const uint8_t *base, uint64_t dev_byte
     if (s.active == 0) {
         return kTxReject;
     }
-    if (!tx_image_ok(base, dev_bytes, off, cap, meta, cur)) {
+    if (!image_ok(base, dev_bytes, off, cap, meta, cur)) {
         return kTxReject;
     }
     if (cur < s.content_len) {
@@ -135,7 +105,7 @@ CIOA_PLACE_FN uint32_t tx_rollback_decide(const uint8_t *base, uint64_t dev_byte
 CIOA_PLACE_FN void tx_rollback_apply(uint8_t *p, const TxState &s, bool checksum, uint32_t crc, uint32_t *crc_cur,
                                      TxState *tx, uint64_t i)
 {
-    tx_put_be32(p + 10, s.content_len);
+    put_be32(p + 10, s.content_len);
     if (checksum) {
         crc_cur[i] = crc;
         p[2] = (uint8_t) crc;
@@ -232,12 +202,12 @@ CIOA_PLACE_FN int32_t tx_commit_one(uint8_t *base, uint64_t dev_bytes, const uin
     const uint64_t off = offs[i];
     uint32_t meta = 0;
     uint64_t content = 0;
-    if (!tx_image_ok(base, dev_bytes, off, caps[i], meta, content)) {
+    if (!image_ok(base, dev_bytes, off, caps[i], meta, content)) {
         return kTxError;
     }
     if (flags & kTxChecksum) {
         uint8_t *p = base + off;
-        tx_put_be32(p + 2, crc_cur[i] ^ 0xffffffffu);
+        put_be32(p + 2, crc_cur[i] ^ 0xffffffffu);
         p[6] = p[7] = p[8] = p[9] = 0;
     }
     const TxState s = tx_load(tx + i);

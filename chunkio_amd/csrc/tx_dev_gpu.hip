@@ -176,11 +176,6 @@ tx_cond_last(int32_t *cond)
     }
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 struct TxArgs {
     const char *who;
     cio_dev_writer *w;
@@ -198,33 +193,26 @@ struct TxArgs {
 // no-op (an empty batch), 0 to go on, CIO_ERROR.
 int check_tx(const TxArgs &a)
 {
-    std::string msg;
     if (a.flags & ~a.allowed) {
-        msg = std::string(a.who) + ": unknown flags";
-        return fail(msg.c_str());
+        return fail_who(a.who, "unknown flags");
     }
     if ((a.flags & CIOA_TX_RECOMPUTE) && !(a.flags & CIO_CHECKSUM)) {
-        msg = std::string(a.who) + ": CIOA_TX_RECOMPUTE needs CIO_CHECKSUM";
-        return fail(msg.c_str());
+        return fail_who(a.who, "CIOA_TX_RECOMPUTE needs CIO_CHECKSUM");
     }
     if (!a.w) {
-        msg = std::string(a.who) + ": null writer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null writer");
     }
     if (a.n == 0) {
         return 1;
     }
     if (!a.dev_base || !a.offs || !a.caps || !a.tx || !a.status || ((a.flags & CIO_CHECKSUM) && !a.crc_cur)) {
-        msg = std::string(a.who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(a.who, "null pointer");
     }
     if (reinterpret_cast<uintptr_t>(a.tx) & 15u) {
-        msg = std::string(a.who) + ": dev_tx must be 16-byte aligned";
-        return fail(msg.c_str());
+        return fail_who(a.who, "dev_tx must be 16-byte aligned");
     }
     if (a.n > a.w->max_chunks) {
-        msg = std::string(a.who) + ": more images than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(a.who, "more images than the writer was created for");
     }
     return 0;
 }
@@ -326,10 +314,10 @@ int cio_file_tx_cond_records_batch_dev(const uint32_t *dev_rec_img, const int32_
         return CIO_OK;
     }
     if (!dev_cond || (n_rec != 0 && (!dev_rec_img || !dev_rec_status))) {
-        return fail((std::string(who) + ": null pointer").c_str());
+        return fail_who(who, "null pointer");
     }
     if (n_img >= 0xffffffffull || n_rec >= 0xffffffffull) {
-        return fail((std::string(who) + ": more than 2^32 - 2 images or records").c_str());
+        return fail_who(who, "more than 2^32 - 2 images or records");
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(tx_cond_clear, dim3(blocks_of(n_img, kTxBlock)), dim3(kTxBlock), 0, s, dev_img_status,

@@ -49,9 +49,7 @@
 // steps, a batch of 2^40 steps) cannot fire in those chains' region passes:
 // every region lies inside an image the header kernel found inside dev_bytes.
 //
-// The layout (cio_layout.h holds it for the host) restated for the device:
-//   0..1 magic C1 00 | 2..9 CRC (8-byte crc_t) | 10..13 content length BE
-//   22..23 metadata length BE | 24.. metadata, then content.
+// The image check and the layout it rests on are image_dev.h.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,25 +67,11 @@ using namespace cioa;
 
 namespace {
 
-constexpr uint32_t kHdrMin = 24;
 constexpr uint32_t kCopyThreads = 256;                 // 4 waves per workgroup
 constexpr uint32_t kCopyWaves = kCopyThreads / kWave;
 constexpr uint32_t kCopyWgPerCu = 8;                   // 32 waves per CU in flight
 constexpr uint64_t kMaxContent = 0xffffffffull;        // the length field is 32 bits
 constexpr uint32_t kMoveWgPerCu = 4;                   // 32 waves per CU, 128 KiB of loads in flight
-
-__device__ __forceinline__ uint32_t be32(const uint8_t *p)
-{
-    return ((uint32_t) p[0] << 24) | ((uint32_t) p[1] << 16) | ((uint32_t) p[2] << 8) | p[3];
-}
-
-__device__ __forceinline__ void put_be32(uint8_t *p, uint32_t v)
-{
-    p[0] = (uint8_t) (v >> 24);
-    p[1] = (uint8_t) (v >> 16);
-    p[2] = (uint8_t) (v >> 8);
-    p[3] = (uint8_t) v;
-}
 
 // crc_update over one byte, bit by bit (raw state, reflected polynomial).
 __device__ __forceinline__ uint32_t crc_byte(uint32_t crc, uint32_t b)
@@ -97,28 +81,6 @@ __device__ __forceinline__ uint32_t crc_byte(uint32_t crc, uint32_t b)
         crc = (crc >> 1) ^ (CIOA_POLY & (0u - (crc & 1u)));
     }
     return crc;
-}
-
-__device__ __forceinline__ bool range_ok(uint64_t off, uint64_t len, uint64_t bytes)
-{
-    return off + len >= off && off + len <= bytes;
-}
-
-// The image checks shared by write and seal: inside dev_bytes, room for a
-// header, the magic, and metadata + content inside the capacity.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap,
-                                         uint32_t &meta, uint64_t &content)
-{
-    if (!range_ok(off, cap, dev_bytes) || cap < kHdrMin) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    meta = ((uint32_t) p[22] << 8) | p[23];
-    content = be32(p + 10);
-    return (uint64_t) kHdrMin + meta + content <= cap;
 }
 
 // ---------------------------------------------------------------- init
@@ -135,14 +97,14 @@ init_headers(uint64_t dev_bytes, const uint64_t *__restrict__ img_offs, const ui
     }
     const uint64_t off = img_offs[i], cap = img_caps[i];
     const uint64_t moff = meta_offs ? meta_offs[i] : 0, m = meta_lens ? meta_lens[i] : 0;
-    bool ok = range_ok(off, cap, dev_bytes) && cap >= kHdrMin;
+    bool ok = range_ok(off, cap, dev_bytes) && cap >= kReadHdr;
     if (ok && m != 0) {
-        ok = m <= 65535u && kHdrMin + m <= cap && range_ok(moff, m, meta_src_bytes);
+        ok = m <= 65535u && kReadHdr + m <= cap && range_ok(moff, m, meta_src_bytes);
     }
     status[i] = ok ? CIO_OK : CIO_ERROR;
     soff[i] = ok && m ? moff : 0;
     slen[i] = ok ? m : 0;
-    dst[i] = ok ? off + kHdrMin : 0;
+    dst[i] = ok ? off + kReadHdr : 0;
     // crc_update(crc_init(), bytes 22..23): 0xBE26ED00 without metadata
     seed[i] = crc_byte(crc_byte(0xffffffffu, (uint32_t) (m >> 8) & 0xffu), (uint32_t) m & 0xffu);
 }
@@ -203,11 +165,11 @@ write_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restric
         uint32_t meta = 0;
         uint64_t content = 0;
         if (image_ok(base, dev_bytes, off, cap, meta, content) && count <= kMaxContent &&
-            content + count <= kMaxContent && (uint64_t) kHdrMin + meta + content + count <= cap &&
+            content + count <= kMaxContent && kReadHdr + meta + content + count <= cap &&
             range_ok(s, count, src_bytes)) {
             so = s;
             sl = count;
-            d = off + kHdrMin + meta + content;
+            d = off + kReadHdr + meta + content;
             nl = (uint32_t) (content + count);
         } else {
             st = CIO_ERROR;
@@ -349,11 +311,11 @@ write_at_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__rest
         uint32_t meta = 0;
         uint64_t content = 0;
         if (image_ok(base, dev_bytes, off, cap, meta, content) && at <= content && count <= kMaxContent &&
-            at + count <= kMaxContent && (uint64_t) kHdrMin + meta + at + count <= cap &&
+            at + count <= kMaxContent && kReadHdr + meta + at + count <= cap &&
             range_ok(s, count, src_bytes)) {
             so = s;
             sl = count;
-            d = off + kHdrMin + meta + at;
+            d = off + kReadHdr + meta + at;
             nl = (uint32_t) (at + count);
             ro = off + 22;
             rl = 2ull + meta + at;
@@ -388,16 +350,16 @@ meta_headers(const uint8_t *base, uint64_t dev_bytes, const uint64_t *__restrict
     uint32_t old = 0;
     uint64_t content = 0;
     const bool ok = image_ok(base, dev_bytes, off, cap, old, content) && m <= 65535u &&
-                    (uint64_t) kHdrMin + m + content <= cap && range_ok(moff, m, meta_src_bytes);
+                    kReadHdr + m + content <= cap && range_ok(moff, m, meta_src_bytes);
     const int64_t delta = ok ? (int64_t) m - (int64_t) old : 0;
     status[i] = ok ? CIO_OK : CIO_ERROR;
     soff[i] = ok && m ? moff : 0;
     slen[i] = ok ? m : 0;
-    dst[i] = ok ? off + kHdrMin : 0;
-    msrc[i] = ok ? off + kHdrMin + old : 0;
+    dst[i] = ok ? off + kReadHdr : 0;
+    msrc[i] = ok ? off + kReadHdr + old : 0;
     mlen[i] = delta != 0 ? content : 0;       // m == old: the metadata is rewritten in place, nothing moves
     mdelta[i] = delta;
-    roff[i] = ok ? off + kHdrMin : 0;
+    roff[i] = ok ? off + kReadHdr : 0;
     rlen[i] = ok ? m + content : 0;
     seed[i] = crc_byte(crc_byte(0xffffffffu, (uint32_t) (m >> 8) & 0xffu), (uint32_t) m & 0xffu);
 }
@@ -573,29 +535,23 @@ int check_args(const char *who, const cio_dev_writer *w, const void *dev_base, c
                const uint64_t *caps, size_t n, int flags, int allowed, const uint32_t *crc_cur,
                const int32_t *status, bool source_ok = true)
 {
-    std::string msg;
     if (flags & ~allowed) {
-        msg = std::string(who) + ": unknown flags";
-        return fail(msg.c_str());
+        return fail_who(who, "unknown flags");
     }
     if ((flags & CIOA_SEAL_RECOMPUTE) && !(flags & CIO_CHECKSUM)) {
-        msg = std::string(who) + ": CIOA_SEAL_RECOMPUTE needs CIO_CHECKSUM";
-        return fail(msg.c_str());
+        return fail_who(who, "CIOA_SEAL_RECOMPUTE needs CIO_CHECKSUM");
     }
     if (!w) {
-        msg = std::string(who) + ": null writer";
-        return fail(msg.c_str());
+        return fail_who(who, "null writer");
     }
     if (n == 0) {
         return 1;
     }
     if (!dev_base || !offs || !caps || !status || ((flags & CIO_CHECKSUM) && !crc_cur) || !source_ok) {
-        msg = std::string(who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(who, "null pointer");
     }
     if (n > w->max_chunks) {
-        msg = std::string(who) + ": more images than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(who, "more images than the writer was created for");
     }
     return 0;
 }

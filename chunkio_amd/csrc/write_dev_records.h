@@ -16,7 +16,7 @@ namespace cioa {
 
 constexpr uint32_t kRecBlock = 1024;                // records per workgroup of the record and place kernels
 constexpr uint64_t kRecMaxContent = 0xffffffffull;  // the length field is 32 bits
-constexpr uint64_t kRecHdr = 24;
+constexpr uint64_t kRecHdr = kReadHdr;
 
 // A partial result of the segmented scan over records [a, b]: flag, whether a
 // run starts in (a, b] or at a; sum, the lengths from the last such start (from
@@ -90,9 +90,9 @@ CIOA_PLACE_FN uint64_t rec_before(bool head, RecSeg carry, RecSeg local)
 // accepted when its image passed the check and the run still fits up to and
 // including r.  A rejected record stays in the sum, so the accepted records of
 // a run are exactly those before the first rejected one.
-CIOA_PLACE_FN bool rec_accept(bool image_ok, uint64_t before, uint64_t v, uint64_t room)
+CIOA_PLACE_FN bool rec_accept(bool img_ok, uint64_t before, uint64_t v, uint64_t room)
 {
-    return image_ok && before != kPlaceOver && place_add(before, v) <= room;
+    return img_ok && before != kPlaceOver && place_add(before, v) <= room;
 }
 
 }  // namespace cioa

@@ -57,24 +57,6 @@ using namespace cioa;
 
 namespace {
 
-// The write path's image check (image_ok in write_dev_gpu.hip), restated: the
-// image inside dev_bytes, room for a header, the magic, and metadata + content
-// inside the capacity.
-__device__ __forceinline__ bool image_ok(const uint8_t *base, uint64_t dev_bytes, uint64_t off, uint64_t cap,
-                                         uint32_t &meta, uint64_t &content)
-{
-    if (off + cap < off || off + cap > dev_bytes || cap < kRecHdr) {
-        return false;
-    }
-    const uint8_t *p = base + off;
-    if (p[0] != 0xc1 || p[1] != 0x00) {
-        return false;
-    }
-    meta = ((uint32_t) p[22] << 8) | p[23];
-    content = ((uint64_t) p[10] << 24) | ((uint64_t) p[11] << 16) | ((uint64_t) p[12] << 8) | p[13];
-    return kRecHdr + meta + content <= cap;
-}
-
 // Image i has a run when i occurs in rec_img: a lower bound in the sorted
 // array.  (Over a malformed array the answer may be wrong; every status of
 // such a batch is overwritten, and the image check guards every read.)
@@ -305,11 +287,6 @@ rec_finish(uint8_t *base, const uint64_t *__restrict__ img_offs, uint32_t n_img,
     p[13] = (uint8_t) nl;
 }
 
-uint32_t blocks_of(size_t n, uint32_t per)
-{
-    return (uint32_t) ((n + per - 1) / per);
-}
-
 // The four bookkeeping kernels: after them dev_rec_status, the record regions
 // (soff, slen, dst) and the images' CRC regions (roff, rlen) are final.
 int launch_bookkeeping(cio_dev_writer *w, const uint8_t *base, uint64_t dev_bytes, const uint64_t *img_offs,
@@ -343,30 +320,24 @@ int check_records(const char *who, const cio_dev_writer *w, const void *dev_base
                   const uint64_t *rec_offs, const uint64_t *rec_lens, size_t n_rec, int flags,
                   const uint32_t *crc_cur, const int32_t *img_status, const int32_t *rec_status)
 {
-    std::string msg;
     if (flags & ~CIO_CHECKSUM) {
-        msg = std::string(who) + ": unknown flags";
-        return fail(msg.c_str());
+        return fail_who(who, "unknown flags");
     }
     if (!w) {
-        msg = std::string(who) + ": null writer";
-        return fail(msg.c_str());
+        return fail_who(who, "null writer");
     }
     if (n_img == 0 || n_rec == 0) {
         return 1;
     }
     if (!dev_base || !offs || !caps || !dev_src || !rec_img || !rec_offs || !rec_lens || !img_status ||
         !rec_status || ((flags & CIO_CHECKSUM) && !crc_cur)) {
-        msg = std::string(who) + ": null pointer";
-        return fail(msg.c_str());
+        return fail_who(who, "null pointer");
     }
     if (n_img > w->max_chunks) {
-        msg = std::string(who) + ": more images than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(who, "more images than the writer was created for");
     }
     if (n_rec > w->max_chunks) {
-        msg = std::string(who) + ": more records than the writer was created for";
-        return fail(msg.c_str());
+        return fail_who(who, "more records than the writer was created for");
     }
     return 0;
 }

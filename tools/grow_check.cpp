@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "grow_dev.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -53,35 +54,6 @@ struct Result {
         return status == o.status && offs == o.offs && caps == o.caps && total == o.total && top == o.top;
     }
 };
-
-void wg_scan(std::vector<uint64_t> &sh, std::vector<uint64_t> &excl, uint64_t &total)
-{
-    std::vector<uint64_t> x(kGrowBlock);
-    for (uint32_t off = 1; off < kGrowBlock; off <<= 1) {
-        for (uint32_t t = 0; t < kGrowBlock; ++t) {
-            x[t] = t >= off ? sh[t - off] : 0;
-        }
-        for (uint32_t t = 0; t < kGrowBlock; ++t) {
-            sh[t] = place_add(x[t], sh[t]);
-        }
-    }
-    for (uint32_t t = 0; t < kGrowBlock; ++t) {
-        excl[t] = t ? sh[t - 1] : 0;
-    }
-    total = sh[kGrowBlock - 1];
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
-}
 
 Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
 {
@@ -114,7 +86,7 @@ Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
             }
             sh[t] = grow_slot(ncap, b.align);
         }
-        wg_scan(sh, excl, rtot[wg]);
+        wg_scan(kGrowBlock, sh, excl, rtot[wg]);
         for (uint32_t t = 0; t < kGrowBlock; ++t) {
             const uint64_t i = (uint64_t) wg * kGrowBlock + t;
             if (i < n) {
@@ -123,18 +95,7 @@ Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
         }
     }
     // grow_scan: one workgroup, pass by pass
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kGrowBlock) {
-        for (uint32_t t = 0; t < kGrowBlock; ++t) {
-            sh[t] = base + t < nb ? rtot[base + t] : 0;
-        }
-        uint64_t pass;
-        wg_scan(sh, excl, pass);
-        for (uint32_t t = 0; t < kGrowBlock && base + t < nb; ++t) {
-            rtot[base + t] = place_add(carry, excl[t]);
-        }
-        carry = place_add(carry, pass);
-    }
+    const uint64_t carry = scan_totals(kGrowBlock, rtot.data(), nb);
     r.total = grow_total(arena[0], b.align, carry);
     // grow_place
     for (uint32_t wg : order_of(nb, order, rng)) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "read_dev_place.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -36,36 +37,6 @@ struct Result {
     bool operator==(const Result &o) const { return offs == o.offs && accepted == o.accepted && total == o.total; }
 };
 
-// The workgroup scan of read_dev_gpu.hip's block_scan_excl, every "thread".
-void wg_scan(std::vector<uint64_t> &sh, std::vector<uint64_t> &excl, uint64_t &total)
-{
-    std::vector<uint64_t> x(kReadBlock);
-    for (uint32_t off = 1; off < kReadBlock; off <<= 1) {
-        for (uint32_t t = 0; t < kReadBlock; ++t) {
-            x[t] = t >= off ? sh[t - off] : 0;
-        }
-        for (uint32_t t = 0; t < kReadBlock; ++t) {
-            sh[t] = place_add(x[t], sh[t]);
-        }
-    }
-    for (uint32_t t = 0; t < kReadBlock; ++t) {
-        excl[t] = t ? sh[t - 1] : 0;
-    }
-    total = sh[kReadBlock - 1];
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
-}
-
 Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
 {
     const uint64_t n = b.len.size();
@@ -78,7 +49,7 @@ Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
             const uint64_t i = (uint64_t) wg * kReadBlock + t;
             sh[t] = i < n && b.ok[i] ? place_slot(b.len[i], b.nul, b.align) : 0;
         }
-        wg_scan(sh, excl, rtot[wg]);
+        wg_scan(kReadBlock, sh, excl, rtot[wg]);
         for (uint32_t t = 0; t < kReadBlock; ++t) {
             const uint64_t i = (uint64_t) wg * kReadBlock + t;
             if (i < n) {
@@ -89,18 +60,7 @@ Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
     }
     // read_scan: one workgroup, pass by pass
     Result r;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kReadBlock) {
-        for (uint32_t t = 0; t < kReadBlock; ++t) {
-            sh[t] = base + t < nb ? rtot[base + t] : 0;
-        }
-        uint64_t pass;
-        wg_scan(sh, excl, pass);
-        for (uint32_t t = 0; t < kReadBlock && base + t < nb; ++t) {
-            rtot[base + t] = place_add(carry, excl[t]);
-        }
-        carry = place_add(carry, pass);
-    }
+    const uint64_t carry = scan_totals(kReadBlock, rtot.data(), nb);
     r.total = carry;
     // read_place
     r.offs.resize(n);

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "pool_dev.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -34,56 +35,6 @@ namespace {
 typedef unsigned __int128 u128;
 const int OK = 0, ERR = -1;
 const uint64_t kUnwritten = 0x7777777777777777ull;
-
-void wg_scan(std::vector<uint64_t> &sh, std::vector<uint64_t> &excl, uint64_t &total)
-{
-    std::vector<uint64_t> x(kPoolBlock);
-    for (uint32_t off = 1; off < kPoolBlock; off <<= 1) {
-        for (uint32_t t = 0; t < kPoolBlock; ++t) {
-            x[t] = t >= off ? sh[t - off] : 0;
-        }
-        for (uint32_t t = 0; t < kPoolBlock; ++t) {
-            sh[t] = place_add(x[t], sh[t]);
-        }
-    }
-    for (uint32_t t = 0; t < kPoolBlock; ++t) {
-        excl[t] = t ? sh[t - 1] : 0;
-    }
-    total = sh[kPoolBlock - 1];
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
-}
-
-// rtot becomes the exclusive scan of the workgroup totals; returns their sum
-// (release_scan / rotate_scan, pass by pass).
-uint64_t scan_totals(std::vector<uint64_t> &rtot)
-{
-    const uint32_t nb = (uint32_t) rtot.size();
-    std::vector<uint64_t> sh(kPoolBlock), excl(kPoolBlock);
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kPoolBlock) {
-        for (uint32_t t = 0; t < kPoolBlock; ++t) {
-            sh[t] = base + t < nb ? rtot[base + t] : 0;
-        }
-        uint64_t pass;
-        wg_scan(sh, excl, pass);
-        for (uint32_t t = 0; t < kPoolBlock && base + t < nb; ++t) {
-            rtot[base + t] = place_add(carry, excl[t]);
-        }
-        carry = place_add(carry, pass);
-    }
-    return carry;
-}
 
 // The pool's arrays: a push beyond the capacity aborts.
 struct PoolArrays {
@@ -178,7 +129,7 @@ RelResult rel_kernels(const Rel &b, int order, std::mt19937_64 &rng)
                 code[i] = c;
             }
         }
-        wg_scan(sh, excl, rtot[wg]);
+        wg_scan(kPoolBlock, sh, excl, rtot[wg]);
         for (uint32_t t = 0; t < kPoolBlock; ++t) {
             const uint64_t i = (uint64_t) wg * kPoolBlock + t;
             if (i < n) {
@@ -187,7 +138,7 @@ RelResult rel_kernels(const Rel &b, int order, std::mt19937_64 &rng)
         }
     }
     // release_scan
-    r.total[0] = scan_totals(rtot);
+    r.total[0] = scan_totals(kPoolBlock, rtot.data(), (uint32_t) rtot.size());
     r.total[1] = pool_kept_total(m, r.total[0], pool_room(pool[0], pool[1], pool[2], pool[3]));
     // release_place
     for (uint32_t wg : order_of(nb, order, rng)) {
@@ -485,7 +436,7 @@ RotResult rot_kernels(const Rot &b, int order, std::mt19937_64 &rng)
             const uint64_t i = (uint64_t) wg * kPoolBlock + t;
             sh[t] = i < n && b.reach[i] ? 1 : 0;
         }
-        wg_scan(sh, excl, rtot[wg]);
+        wg_scan(kPoolBlock, sh, excl, rtot[wg]);
         for (uint32_t t = 0; t < kPoolBlock; ++t) {
             const uint64_t i = (uint64_t) wg * kPoolBlock + t;
             if (i < n) {
@@ -493,7 +444,7 @@ RotResult rot_kernels(const Rot &b, int order, std::mt19937_64 &rng)
             }
         }
     }
-    r.total[1] = scan_totals(rtot);
+    r.total[1] = scan_totals(kPoolBlock, rtot.data(), (uint32_t) rtot.size());
     // rotpool_place
     for (uint32_t wg : order_of(nb, order, rng)) {
         for (uint32_t t = 0; t < kPoolBlock; ++t) {

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "pool_set.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -36,54 +37,6 @@ typedef unsigned __int128 u128;
 const int OK = 0, ERR = -1;
 const uint64_t kUnwritten = 0x7777777777777777ull;
 long g_cases = 0;
-
-void wg_scan(std::vector<uint64_t> &sh, std::vector<uint64_t> &excl, uint64_t &total)
-{
-    std::vector<uint64_t> x(kSetBlock);
-    for (uint32_t off = 1; off < kSetBlock; off <<= 1) {
-        for (uint32_t t = 0; t < kSetBlock; ++t) {
-            x[t] = t >= off ? sh[t - off] : 0;
-        }
-        for (uint32_t t = 0; t < kSetBlock; ++t) {
-            sh[t] = place_add(x[t], sh[t]);
-        }
-    }
-    for (uint32_t t = 0; t < kSetBlock; ++t) {
-        excl[t] = t ? sh[t - 1] : 0;
-    }
-    total = sh[kSetBlock - 1];
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
-}
-
-// totals_scan of the kernels, pass by pass: v becomes its exclusive scan.
-uint64_t scan_totals(uint64_t *v, uint32_t nb)
-{
-    std::vector<uint64_t> sh(kSetBlock), excl(kSetBlock);
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kSetBlock) {
-        for (uint32_t t = 0; t < kSetBlock; ++t) {
-            sh[t] = base + t < nb ? v[base + t] : 0;
-        }
-        uint64_t pass;
-        wg_scan(sh, excl, pass);
-        for (uint32_t t = 0; t < kSetBlock && base + t < nb; ++t) {
-            v[base + t] = place_add(carry, excl[t]);
-        }
-        carry = place_add(carry, pass);
-    }
-    return carry;
-}
 
 // class_rank of the kernels for workgroup b: cls[i] of its entries (kSetNone
 // beyond n).  rank[i] and the workgroup's K counts into tab.
@@ -139,7 +92,7 @@ void class_rank_wg(uint32_t b, uint32_t nb, uint64_t n, const std::vector<uint32
 void class_scan(uint64_t *tab, uint32_t nb, uint32_t n_cls, uint64_t *reach)
 {
     const uint32_t words = n_cls * nb;
-    const uint64_t all = scan_totals(tab, words);            // one linear scan of the class-major table
+    const uint64_t all = scan_totals(kSetBlock, tab, words);            // one linear scan of the class-major table
     uint64_t first[kPoolSetMax];
     for (uint32_t k = 0; k < n_cls; ++k) {
         first[k] = tab[set_tab_at(k, 0, nb)];
@@ -357,7 +310,7 @@ RelResult rel_kernels(const std::vector<Ent> &ent, bool has_count, uint64_t coun
         }
         if (compact) {
             uint64_t total;
-            wg_scan(sh, excl, total);
+            wg_scan(kSetBlock, sh, excl, total);
             rtot[b] = total;
             for (uint32_t t = 0; t < kSetBlock; ++t) {
                 const uint64_t i = (uint64_t) b * kSetBlock + t;
@@ -368,7 +321,7 @@ RelResult rel_kernels(const std::vector<Ent> &ent, bool has_count, uint64_t coun
         }
     }
     if (compact) {
-        scan_totals(rtot.data(), nb);             // relset_kscan
+        scan_totals(kSetBlock, rtot.data(), nb);             // relset_kscan
         for (uint32_t b : order_of(nb, order, rng)) {         // relset_kmove
             for (uint32_t t = 0; t < kSetBlock; ++t) {
                 const uint64_t i = (uint64_t) b * kSetBlock + t;
@@ -633,7 +586,7 @@ GrowResult grow_kernels(const std::vector<Img> &im, const Set &s, uint64_t top, 
             code[i] = c;
         }
         uint64_t total;
-        wg_scan(sh, excl, total);
+        wg_scan(kSetBlock, sh, excl, total);
         rtot[b] = total;
         for (uint32_t t = 0; t < kSetBlock; ++t) {
             const uint64_t i = (uint64_t) b * kSetBlock + t;
@@ -643,7 +596,7 @@ GrowResult grow_kernels(const std::vector<Img> &im, const Set &s, uint64_t top, 
         }
     }
     // growset_ascan
-    r.total[0] = grow_total(arena[0], align, scan_totals(rtot.data(), nb));
+    r.total[0] = grow_total(arena[0], align, scan_totals(kSetBlock, rtot.data(), nb));
     // growset_place
     for (uint32_t b : order_of(nb, order, rng)) {
         for (uint32_t t = 0; t < kSetBlock; ++t) {

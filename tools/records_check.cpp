@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "write_dev_records.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -60,18 +61,6 @@ void wg_scan(std::vector<RecSeg> &sh, std::vector<RecSeg> &excl, RecSeg &total)
         excl[t] = t ? sh[t - 1] : rec_none();
     }
     total = sh[kRecBlock - 1];
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
 }
 
 Result kernels(const Batch &b, int order, std::mt19937_64 &rng)

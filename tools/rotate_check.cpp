@@ -1,5 +1,5 @@
 // rotate_check.cpp -- rotating full chunk images (rotate_dev.h: the text the
-// kernels rotate_sums, rotate_headers, rotate_scan, rotate_place and
+// kernels rotate_sums_wave, rotate_headers, rotate_scan, rotate_place and
 // rotate_commit run), stand-alone on the host under ASan + UBSan: no GPU, no
 // HIP.  `make rotatecheck`.
 //
@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "rotate_dev.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -59,35 +60,6 @@ struct Result {
 };
 
 const uint64_t kUnwritten = 0x7777777777777777ull;
-
-void wg_scan(std::vector<uint64_t> &sh, std::vector<uint64_t> &excl, uint64_t &total)
-{
-    std::vector<uint64_t> x(kRotBlock);
-    for (uint32_t off = 1; off < kRotBlock; off <<= 1) {
-        for (uint32_t t = 0; t < kRotBlock; ++t) {
-            x[t] = t >= off ? sh[t - off] : 0;
-        }
-        for (uint32_t t = 0; t < kRotBlock; ++t) {
-            sh[t] = place_add(x[t], sh[t]);
-        }
-    }
-    for (uint32_t t = 0; t < kRotBlock; ++t) {
-        excl[t] = t ? sh[t - 1] : 0;
-    }
-    total = sh[kRotBlock - 1];
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
-}
 
 // The list arrays hold min(list_cap, a bound) entries: exactly the capacity
 // where that can be allocated.
@@ -137,7 +109,7 @@ Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
             }
             sh[t] = hl ? 1 : 0;
         }
-        wg_scan(sh, excl, rtot[wg]);
+        wg_scan(kRotBlock, sh, excl, rtot[wg]);
         for (uint32_t t = 0; t < kRotBlock; ++t) {
             const uint64_t i = (uint64_t) wg * kRotBlock + t;
             if (i < n) {
@@ -146,18 +118,7 @@ Result kernels(const Batch &b, int order, std::mt19937_64 &rng)
         }
     }
     // rotate_scan: one workgroup, pass by pass
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kRotBlock) {
-        for (uint32_t t = 0; t < kRotBlock; ++t) {
-            sh[t] = base + t < nb ? rtot[base + t] : 0;
-        }
-        uint64_t pass;
-        wg_scan(sh, excl, pass);
-        for (uint32_t t = 0; t < kRotBlock && base + t < nb; ++t) {
-            rtot[base + t] = place_add(carry, excl[t]);
-        }
-        carry = place_add(carry, pass);
-    }
+    const uint64_t carry = scan_totals(kRotBlock, rtot.data(), nb);
     r.total[0] = rot_total(arena[0], b.align, carry, slot);
     r.total[1] = carry;
     // rotate_place

@@ -26,14 +26,14 @@ first event of every call.
                                                rotate_place
   d    a batch in which nothing is full        the same images with 64 bytes of room each: the fixed cost every
                                                guarded append pays
-  e1w  the pre-reduced sums, distinct images   section 6 of the records variant: rotate_clear + rotate_sums_wave,
+  e1w  the pre-reduced sums, distinct images   section 6 of the records variant: grow_clear + rotate_sums_wave,
                                                one record per image
   e1m  the same again                          the A/A spread of the sums legs
   e2w  the pre-reduced sums, one image         all records to image 0: one atomic per wave
-  e1n  the sums the calls run, distinct        section 1: rotate_clear + rotate_sums (plain atomics)
-  e2n  the sums the calls run, one image
-  e1p  the parent's sums, distinct images      cioa_debug_grow_events section 1: grow_clear + grow_need (this
-  e2p  the parent's sums, one image            library's; the unit's device code is the parent's byte for byte)
+  e1n  the sums the calls run, distinct        section 1: grow_clear + grow_need (plain atomics; the grow unit's
+  e2n  the sums the calls run, one image       kernels through launch_need_sums)
+  e1p  the same kernels through grow's hook,   cioa_debug_grow_events section 1: grow_clear + grow_need, what
+  e2p  distinct images / one image             r15 measured as "the parent's sums"
 
 a - b is what the device-side decision costs over the parent's two calls.
 """

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "sort_records.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -25,18 +26,6 @@ struct Sorted {
     std::vector<uint32_t> key, idx;
     bool operator==(const Sorted &o) const { return key == o.key && idx == o.idx; }
 };
-
-std::vector<uint32_t> order_of(uint32_t n, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(n);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
-}
 
 // Record r of the pass: load_key of sort_records_gpu.hip.
 uint32_t load_key(const std::vector<uint32_t> &img, const std::vector<uint32_t> &kin, uint32_t pass, uint32_t n_img,

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "tx_dev.h"
+#include "check_scan.h"
 
 using namespace cioa;
 
@@ -60,18 +61,6 @@ uint32_t crc_bytes(uint32_t crc, const uint8_t *p, uint64_t len)
         }
     }
     return crc;
-}
-
-std::vector<uint32_t> order_of(uint32_t nb, int order, std::mt19937_64 &rng)
-{
-    std::vector<uint32_t> o(nb);
-    std::iota(o.begin(), o.end(), 0u);
-    if (order == 1) {
-        std::reverse(o.begin(), o.end());
-    } else if (order == 2) {
-        std::shuffle(o.begin(), o.end(), rng);
-    }
-    return o;
 }
 
 // Everything a call may touch.
@@ -534,7 +523,7 @@ uint64_t check_huge()
                         uint32_t m2 = 0;
                         uint64_t c2 = 0;
                         CHECK(st1 == OK && tx[0].active == 0 && crc_cur == 0x12345678u &&
-                                  tx_image_ok(buf.data(), dev_bytes, off, cap, m2, c2) && c2 == kept && m2 == meta,
+                                  image_ok(buf.data(), dev_bytes, off, cap, m2, c2) && c2 == kept && m2 == meta,
                               "huge: rollback");
                         CHECK(tx_begin_one(buf.data(), dev_bytes, &off, &cap, 0, &crc_cur, tx.data()) == OK &&
                                   tx[0].active == 1 && tx[0].content_len == kept && tx[0].meta_len == meta,
