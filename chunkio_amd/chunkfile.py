@@ -48,6 +48,12 @@ are cio_chunk_tx_begin / _rollback / _commit (src/cio_chunk.c:423-502) on
 images in device memory, and tx_cond_records_batch_dev turns the statuses of a
 records append into the per-image condition of an all-or-nothing append
 (include/chunkio_amd/cio_write_dev_tx.h).
+
+alloc_set_batch_dev hands out fresh slots of given sizes from a pool set and
+the arena, and load_paths_dev / store_paths_dev move batches of chunks between
+chunk files and images in device memory: cio_chunk_up, and cio_file_sync +
+cio_chunk_down (src/cio_chunk.c:556-605), for device images
+(include/chunkio_amd/cio_persist_dev.h).
 """
 import ctypes
 import os
@@ -75,6 +81,8 @@ CIOA_TX_RECOMPUTE, CIOA_TX_ZERO = 256, 512      # cio_write_dev_tx.h
 CIOA_RELEASE_ZERO, CIOA_RELEASE_COMPACT = 1, 2  # cio_write_dev_pool.h
 CIOA_POOL_SET_MAX = 8           # cio_write_dev_pool_set.h
 COALESCE_DRY = 1                # cio_write_dev_coalesce.h: CIOA_COALESCE_DRY
+CIOA_ALLOC_ZERO, CIOA_LOAD_ZERO = 1, 512        # cio_persist_dev.h
+CIOA_STORE_TRIM, CIOA_STORE_SYNC = 1, 2
 
 HDR_MIN = 24
 CONTENT_OFFSET = 22
@@ -728,6 +736,120 @@ def coalesce_set_dev(writer, dev_bytes, set, target, align=16, flags=0, total=No
                                               int(align), int(flags), _ptr(total), _stream_ptr(stream))
     _lib.check(rc, "cio_file_coalesce_set_dev")
     return total
+
+
+def _set_or_none(set):
+    return _set_args(set) if set is not None else (None, None, None, 0, 0)
+
+
+def alloc_set_batch_dev(writer, base, need, arena, set=None, gate=None, align=16, flags=0, out_offs=None,
+                        out_caps=None, total=None, status=None, stream=None):
+    """n fresh slots of need[i] bytes each out of a pool set, then the arena
+    (cio_file_alloc_set_batch_dev): entry i, when gate is None or gate[i] ==
+    CIO_OK and need[i] >= 24, takes the top entry of the smallest usable class
+    that holds its need, with the entry's whole capacity; when the class is
+    empty an arena slot of the class's size, and without a class one of its
+    need.  set: (set_offs, set_caps, set, n_cls, stride) as from
+    pool_set_state, or None for the arena alone; flags: 0 or CIOA_ALLOC_ZERO
+    (zero every slot taken; without it no byte of base is touched).  Returns
+    (status int32, total int64[2 + n_cls], out_offs int64, out_caps int64)
+    cuda tensors without waiting: an entry without a slot has out_offs -1
+    (UINT64_MAX), out_caps 0 and CIO_ERROR; total as grow_set_batch_dev's."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = int(need.numel())
+    dev = base.device
+    if total is None:
+        total = torch.zeros(2 + (int(set[3]) if set is not None else 0), dtype=torch.int64, device=dev)
+    status = _status_out(status, n, dev)
+    out_offs, out_caps = _u64_out(out_offs, n, dev), _u64_out(out_caps, n, dev)
+    rc = _lib.lib().cio_file_alloc_set_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(need), _ptr(gate), n, _ptr(arena), *_set_or_none(set),
+        int(align), int(flags), _ptr(out_offs), _ptr(out_caps), _ptr(total), _ptr(status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_alloc_set_batch_dev")
+    return status[:n], total, out_offs[:n], out_caps[:n]
+
+
+def persist_round_max(stage_bytes):
+    """The largest file (load) or image (store) a stage of stage_bytes takes
+    (cio_file_persist_round_max)."""
+    return int(_lib.lib().cio_file_persist_round_max(int(stage_bytes)))
+
+
+def persist_rounds(sizes, stage_bytes):
+    """How load_paths_dev and store_paths_dev cut files of these sizes into
+    rounds of the stage (cio_file_persist_rounds).  Returns (rounds, round_of
+    uint32 array): round_of[i] is 0xffffffff for a file larger than
+    persist_round_max(stage_bytes)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    round_of = np.zeros(max(len(sizes), 1), np.uint32)
+    rc = _lib.lib().cio_file_persist_rounds(sizes.ctypes.data, len(sizes), int(stage_bytes), round_of.ctypes.data)
+    if rc < 0:
+        _lib.check(rc, "cio_file_persist_rounds")
+    return rc, round_of[:len(sizes)]
+
+
+def persist_trim():
+    """Free the pinned staging and the device scratch that load_paths_dev and
+    store_paths_dev keep between calls (cio_file_persist_trim)."""
+    _lib.lib().cio_file_persist_trim()
+
+
+def _paths(paths):
+    return (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+
+
+def load_paths_dev(writer, base, paths, stage, arena, set=None, flags=CIO_CHECKSUM, align=16, img_offs=None,
+                   img_caps=None, crc_cur=None, dev_status=None, stream=None):
+    """Chunk files into device memory, cio_chunk_up for a batch
+    (cio_file_load_paths_dev): the files are read in rounds of the stage (a
+    uint8 cuda tensor), verified there, given slots of their file sizes out of
+    the set and the arena, and copied into them.  flags: 0 or CIO_CHECKSUM,
+    with CIOA_LOAD_ZERO the slots' tails are zeroed.  WAITS for the work.
+    Returns (status int32, error int32, fs_sizes uint64) numpy arrays and
+    (img_offs int64, img_caps int64, crc_cur int32, dev_status int32) cuda
+    tensors: a file that was not loaded has img_offs -1 and img_caps 0."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n = len(paths)
+    dev = base.device
+    img_offs, img_caps = _u64_out(img_offs, n, dev), _u64_out(img_caps, n, dev)
+    if crc_cur is None:
+        crc_cur = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    dev_status = _status_out(dev_status, n, dev)
+    st, er = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    fs = np.zeros(max(n, 1), np.uint64)
+    rc = _lib.lib().cio_file_load_paths_dev(
+        writer._handle, _ptr(base), _nbytes(base), ctypes.cast(_paths(paths), ctypes.c_void_p), n, int(flags),
+        _ptr(stage), _nbytes(stage), _ptr(arena), *_set_or_none(set), int(align), _ptr(img_offs), _ptr(img_caps),
+        _ptr(crc_cur), _ptr(dev_status), st.ctypes.data, er.ctypes.data, fs.ctypes.data, _stream_ptr(stream))
+    _lib.check(rc, "cio_file_load_paths_dev")
+    return st[:n], er[:n], fs[:n], img_offs[:n], img_caps[:n], crc_cur[:n], dev_status[:n]
+
+
+def store_paths_dev(writer, base, img_offs, img_caps, paths, stage, gate=None, flags=0, page=4096, dev_status=None,
+                    stream=None):
+    """Chunk images in device memory into chunk files, cio_file_sync +
+    cio_chunk_down for a batch (cio_file_store_paths_dev): file i holds image
+    i's used bytes followed by zeros up to img_caps[i], or with
+    CIOA_STORE_TRIM up to the used bytes rounded up to page (1: exact).  No CRC
+    is computed: seal and verify_batch_dev ahead, and pass verify's status as
+    gate.  A rejected image creates no file.  CIOA_STORE_SYNC: fdatasync.
+    WAITS for the work.  Returns (status int32, file_sizes uint64) numpy arrays
+    and dev_status, the int32 cuda tensor release_set_batch_dev takes as its
+    gate."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(img_offs.numel())
+    if len(paths) != n:
+        raise ValueError("one path per image")
+    dev_status = _status_out(dev_status, n, base.device)
+    st, fs = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
+    rc = _lib.lib().cio_file_store_paths_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(img_offs), _ptr(img_caps), n, _ptr(gate),
+        ctypes.cast(_paths(paths), ctypes.c_void_p), int(flags), int(page), _ptr(stage), _nbytes(stage),
+        st.ctypes.data, fs.ctypes.data, _ptr(dev_status), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_store_paths_dev")
+    return st[:n], fs[:n], dev_status[:n]
 
 
 def tx_state(n, device):

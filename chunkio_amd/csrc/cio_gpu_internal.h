@@ -9,6 +9,8 @@
 // tx_dev_gpu.hip: transactions on images; pool_dev_gpu.hip: recycling drained
 // slots through a pool; pool_set_gpu.hip: the size-classed set of such pools;
 // coalesce_gpu.hip: coalescing that set's adjacent free slots;
+// alloc_set_gpu.hip: fresh slots out of that set and the device steps of a
+// load; persist_host.hip: images down to chunk files and up again;
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host
@@ -230,6 +232,27 @@ int grow_launch_front(const GrowArgs &a, hipStream_t s, const SectionEvents *ev 
 // (skey, sidx) arena pairs, the histogram table in stab.  *sorted: the pair
 // that holds the result.  rec_img must be none of those arenas.
 int sort_launch(cio_dev_writer *w, const uint32_t *rec_img, size_t n_img, size_t n_rec, int *sorted, hipStream_t s);
+
+// The device arrays of one round of a load (persist_host.hip), n entries each:
+// what the host uploads (the files' places in the stage, their sizes, whether
+// each was read in full), what verify and the allocation leave, and the call's
+// outputs for the round's files.
+struct LoadRound {
+    const uint64_t *soffs, *sizes;
+    const int32_t *pre, *vst, *ast;
+    const uint64_t *aoffs, *acaps;
+    const uint32_t *vcrc;
+    const uint64_t *vcontent;
+    uint64_t *img_offs, *img_caps;
+    uint32_t *crc_cur;
+    int32_t *status;
+};
+
+// The back of a round of a load, behind verify and the allocation
+// (alloc_set_gpu.hip): the copy from the stage into the slots, the adopt step,
+// and with `zero` the fill of [size, cap) of every slot taken.
+int load_launch_back(cio_dev_writer *w, void *dev_base, uint64_t dev_bytes, const void *dev_stage,
+                     uint64_t stage_bytes, size_t n, bool zero, const LoadRound &r, hipStream_t s);
 
 }  // namespace cioa
 
