@@ -19,7 +19,7 @@ HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -std=c++17 -Wall $(INC) -munsafe-fp
             -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-kernarg-preload-count=9
 
 COBJS   := $(BLD)/host_copy.o $(BLD)/crc32_host.o $(BLD)/crc32_scalar.o $(BLD)/cio_verify.o $(BLD)/cio_sync.o $(BLD)/cioa_chunk.o $(BLD)/crc_route.o $(BLD)/crc_cpu_batch.o $(BLD)/cio_sha1.o
-HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o $(BLD)/alloc_set_gpu.o $(BLD)/persist_host.o
+HOBJS   := $(BLD)/crc32_gpu.o $(BLD)/probe_gpu.o $(BLD)/gpu_runtime.o $(BLD)/crc_plan.o $(BLD)/host_pipeline.o $(BLD)/sha1_gpu.o $(BLD)/devplan_gpu.o $(BLD)/write_dev_gpu.o $(BLD)/read_dev_gpu.o $(BLD)/write_records_gpu.o $(BLD)/sort_records_gpu.o $(BLD)/grow_dev_gpu.o $(BLD)/rotate_dev_gpu.o $(BLD)/tx_dev_gpu.o $(BLD)/pool_dev_gpu.o $(BLD)/pool_set_gpu.o $(BLD)/coalesce_gpu.o $(BLD)/alloc_set_gpu.o $(BLD)/persist_host.o $(BLD)/route_gpu.o
 
 CTEST   := tests/c/bin
 REF_INC := /root/reference/include/chunkio/cio_crc32.h
@@ -154,8 +154,13 @@ $(BLD)/asm/%.s: $(SRC)/%.hip $(wildcard $(SRC)/*.h) $(wildcard include/*/*.h)
 #                  exactly the set's extent
 #   persistcheck   persist_plan.h: the round planner and the file-size rule at
 #                  every boundary, against a restatement in 128-bit arithmetic
+#   routecheck     route.h: the tag rule at every boundary, and the lower bound,
+#                  the candidates' walk and the choice over sorted arrays, shuffled
+#                  arrays, arrays with entries >= n, all-equal keys and the keys 0
+#                  and 0xffffffff, the arrays of exactly n entries, against a
+#                  linear restatement
 SANFLAGS := -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined
-CHECKS   := plan copy move place records sort grow rotate tx pool pool_set coalesce image alloc persist
+CHECKS   := plan copy move place records sort grow rotate tx pool pool_set coalesce image alloc persist route
 CHECKTGT := $(foreach c,$(CHECKS),$(subst _,,$(c))check)
 
 # plan_check links the planner and the host CRC it calls.

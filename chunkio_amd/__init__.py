@@ -32,6 +32,9 @@ Layers:
                                                    grow_set_records_batch_dev;
                                                    cio_write_dev_coalesce.h:
                                                    coalesce_set_dev;
+                                                   cio_route_dev.h:
+                                                   route_dir, route_build_dev,
+                                                   route_records_batch_dev;
                                                    cio_persist_dev.h:
                                                    alloc_set_batch_dev, load_paths_dev,
                                                    store_paths_dev, persist_round_max,
@@ -60,6 +63,7 @@ from .chunkfile import (  # noqa: F401,E402
     CIOA_POOL_SET_MAX, grow_set_batch_dev, grow_set_records_batch_dev, pool_set_class, pool_set_state,
     release_set_batch_dev,
     COALESCE_DRY, coalesce_set_dev,
+    route_build_dev, route_dir, route_records_batch_dev,
     CIOA_ALLOC_ZERO, CIOA_LOAD_ZERO, CIOA_STORE_SYNC, CIOA_STORE_TRIM, alloc_set_batch_dev, load_paths_dev,
     persist_round_max, persist_rounds, persist_trim, store_paths_dev,
     tx_begin_batch_dev, tx_commit_batch_dev, tx_cond_records_batch_dev, tx_rollback_batch_dev, tx_state,

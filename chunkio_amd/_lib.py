@@ -59,6 +59,8 @@ EXPORTS = (
     "cio_file_release_set_batch_dev", "cio_file_grow_set_batch_dev", "cio_file_grow_set_records_batch_dev",
     # include/chunkio_amd/cio_write_dev_coalesce.h
     "cio_file_coalesce_set_dev",
+    # include/chunkio_amd/cio_route_dev.h
+    "cio_file_route_build_dev", "cio_file_route_records_batch_dev",
     # include/chunkio_amd/cio_persist_dev.h
     "cio_file_alloc_set_batch_dev", "cio_file_persist_round_max", "cio_file_persist_rounds",
     "cio_file_load_paths_dev", "cio_file_store_paths_dev", "cio_file_persist_trim",
@@ -177,6 +179,10 @@ def _bind(lib):
                                                                ctypes.c_uint64, ctypes.c_int, V, V, V, V, V]),
         "cio_file_coalesce_set_dev": (ctypes.c_int, [V, ctypes.c_uint64, V, V, V, ctypes.c_size_t, ctypes.c_uint64,
                                                      ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, V, V]),
+        "cio_file_route_build_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V, V, V]),
+        "cio_file_route_records_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V, V, V,
+                                                            V, ctypes.c_uint64, V, V, ctypes.c_size_t,
+                                                            ctypes.c_uint32, ctypes.c_int, V, V, V, V, V]),
         "cio_file_alloc_set_batch_dev": (ctypes.c_int, [V, V, ctypes.c_uint64, V, V, ctypes.c_size_t, V, V, V, V,
                                                         ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
                                                         ctypes.c_int, V, V, V, V, V]),

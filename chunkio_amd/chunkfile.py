@@ -738,6 +738,75 @@ def coalesce_set_dev(writer, dev_bytes, set, target, align=16, flags=0, total=No
     return total
 
 
+def route_dir(n_img, device):
+    """An unbuilt directory for n_img images (cio_route_dev.h): (dir_keys,
+    dir_imgs, dir_hdr) int32 cuda tensors holding uint32 bits -- the two arrays
+    of n_img words and the four header words [n_img, images that passed the
+    check, 0, 0].  route_build_dev fills it."""
+    import torch
+    keys = torch.zeros(max(int(n_img), 1), dtype=torch.int32, device=device)
+    imgs = torch.zeros(max(int(n_img), 1), dtype=torch.int32, device=device)
+    hdr = torch.zeros(4, dtype=torch.int32, device=device)
+    return keys, imgs, hdr
+
+
+def route_build_dev(writer, base, offs, caps, dir, stream=None):
+    """Build the directory of the images base[offs[i]:offs[i] + caps[i]]
+    (cio_file_route_build_dev): dir = (dir_keys, dir_imgs, dir_hdr) as from
+    route_dir(n, device) becomes the stable sort of (key_i, i) by key, key_i
+    the raw CRC-32 state of image i's metadata -- of the empty string for an
+    image that fails the image check -- and the header.  No byte of base is
+    written.  Returns dir without waiting."""
+    from .crc32 import _ptr, _stream_ptr
+    n = int(offs.numel())
+    keys, imgs, hdr = dir
+    if min(int(keys.numel()), int(imgs.numel())) < n or keys.element_size() != 4 or imgs.element_size() != 4:
+        raise ValueError("dir must hold 32-bit tensors of n_img elements")
+    rc = _lib.lib().cio_file_route_build_dev(writer._handle, _ptr(base), _nbytes(base), _ptr(offs), _ptr(caps), n,
+                                             _ptr(keys), _ptr(imgs), _ptr(hdr), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_route_build_dev")
+    return dir
+
+
+def route_records_batch_dev(writer, base, offs, caps, dir, tags, tag_offs, tag_lens, miss_img, gate=None,
+                            miss_list=False, flags=0, stream=None):
+    """Route record r to the image whose metadata equals its tag,
+    tags[tag_offs[r]:+tag_lens[r]] (cio_file_route_records_batch_dev), through
+    the directory dir of route_build_dev: the lowest such image i that passes
+    the image check now and whose gate (int32 statuses, optional) is CIO_OK.
+    rec_img[r] = i with status CIO_OK; a well-formed tag without a match gets
+    miss_img and CIO_RETRY, a malformed one (longer than 65535 bytes, or
+    outside tags) miss_img and CIO_ERROR.  A stale directory can only lose
+    matches; one of another size makes every record CIO_ERROR.  tags: uint8
+    cuda tensor, or None when every tag is empty.  miss_list: True, or an
+    int32 cuda tensor of n_rec to reuse -- its first total[1] entries become
+    the missed record indices in ascending order.  Returns (rec_img int32
+    holding uint32 indices, rec_status int32, total int64[3]: matched, missed,
+    malformed[, miss_list]) cuda tensors without waiting; rec_img is what the
+    rotate, grow and append calls take."""
+    import torch
+    from .crc32 import _ptr, _stream_ptr
+    n_img, n_rec = int(offs.numel()), int(tag_offs.numel())
+    keys, imgs, hdr = dir
+    dev = hdr.device
+    rec_img = torch.zeros(max(n_rec, 1), dtype=torch.int32, device=dev)
+    rec_status = torch.zeros(max(n_rec, 1), dtype=torch.int32, device=dev)
+    total = torch.zeros(3, dtype=torch.int64, device=dev)
+    want_list = miss_list is not None and miss_list is not False
+    if want_list and miss_list is True:
+        miss_list = torch.zeros(max(n_rec, 1), dtype=torch.int32, device=dev)
+    if want_list and (miss_list.element_size() != 4 or miss_list.numel() < n_rec):
+        raise ValueError("miss_list must be a 32-bit tensor of n_rec elements")
+    rc = _lib.lib().cio_file_route_records_batch_dev(
+        writer._handle, _ptr(base), _nbytes(base), _ptr(offs), _ptr(caps), n_img, _ptr(gate), _ptr(keys), _ptr(imgs),
+        _ptr(hdr), _ptr(tags), 0 if tags is None else _nbytes(tags), _ptr(tag_offs), _ptr(tag_lens), n_rec,
+        int(miss_img) & 0xffffffff, int(flags), _ptr(rec_img), _ptr(rec_status),
+        _ptr(miss_list) if want_list else None, _ptr(total), _stream_ptr(stream))
+    _lib.check(rc, "cio_file_route_records_batch_dev")
+    out = (rec_img[:n_rec], rec_status[:n_rec], total)
+    return out + (miss_list[:n_rec],) if want_list else out
+
+
 def _set_or_none(set):
     return _set_args(set) if set is not None else (None, None, None, 0, 0)
 

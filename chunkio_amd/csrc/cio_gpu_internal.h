@@ -11,6 +11,7 @@
 // coalesce_gpu.hip: coalescing that set's adjacent free slots;
 // alloc_set_gpu.hip: fresh slots out of that set and the device steps of a
 // load; persist_host.hip: images down to chunk files and up again;
+// route_gpu.hip: routing records to images by their metadata;
 // host_pipeline.hip: the host-memory / file
 // batch pipeline).
 // Everything that needs no HIP type -- geometry, the plan image, the host

@@ -43,7 +43,9 @@
  *
  * Not here: a CRC per record, per-record destinations.  Growing the images for
  * a record list is cio_file_grow_records_batch_dev (cio_write_dev_grow.h),
- * queued ahead; it takes the list in any order too.
+ * queued ahead; it takes the list in any order too.  Producing dev_rec_img
+ * from records that carry a tag is cio_file_route_records_batch_dev
+ * (cio_route_dev.h), queued ahead of both.
  */
 #ifndef CIO_WRITE_DEV_UNGROUPED_H
 #define CIO_WRITE_DEV_UNGROUPED_H
